@@ -3,9 +3,12 @@
 
 A step is one forward NTT over BN254 Fr on HBM-resident synthetic data
 (BASELINE.md generator) with 2^24 points per GPU.  `value` = field elements of
-the transform per second.  The N=1 line also carries the Merkle leaves/s (2^24
-32-B leaves), the 2^20 forward+inverse pair (config 2) and an FRI prove
-wall-clock.
+the transform per second.  A plain run sets up, warms up, times the K steps and
+prints the line; `--dump-outputs DIR` also writes what the last timed step
+computed.  With `--full` the line also carries the parity flags of the timed
+path, the Merkle leaves/s (2^24 32-B leaves), the 2^20 forward+inverse pair
+(config 2), an FRI prove wall-clock, the end-to-end proofs, the CPU baselines
+and, for N > 1, the per-phase roofline and the distributed extras.
 
 N > 1 GPUs: one process per GPU (torch.distributed.run, backend "nccl" = RCCL);
 the GPUs jointly transform ONE 2^(24+log2 N)-point vector with the one-exchange
@@ -58,11 +61,24 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--log-n", type=int, default=LOG_N)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: parity of the timed path, the extras "
+                         "(other sizes, Merkle, FRI, full proofs, power), the CPU baselines, the N > 1 phases")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (one GPU)")
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks and rendezvous only (CPU test of the --gpus N launcher)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes the one-GPU transform's output: use --gpus 1")
+    if not args.full:
+        # a plain run measures the headline figure only
+        args.no_extras = args.no_cpu_baseline = True
+    return args
 
 
 def _free_port() -> int:
@@ -135,6 +151,27 @@ def host_cpus():
 def synthetic(n, seed):
     import oracle as O  # the synthetic generator only; not the checker here
     return O.random_elements(n, seed)
+
+
+DUMP_ROWS = 1 << 18            # rows of the --dump-outputs sample: 2^18 x 8 limbs x 8 B = 16 MiB
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_outputs(out_dir, buf, n):
+    """--dump-outputs: the transform the last timed step left in `buf` (n field elements, four 64-bit
+    words each, natural order), as float64 arrays.  ntt_output_rows.npy holds the row numbers written
+    (every row up to DUMP_ROWS of them, else a fixed seeded sample in ascending order) and
+    ntt_output_u32_limbs.npy those rows as eight 32-bit limbs each, least significant first: every
+    limb is below 2^32, so float64 holds it exactly and two builds can be compared for equality."""
+    os.makedirs(out_dir, exist_ok=True)
+    if n <= DUMP_ROWS:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_ROWS, dtype=np.int64))
+    got = buf.view(n, 4)[torch.from_numpy(rows).to(buf.device)].cpu().numpy()
+    limbs = np.ascontiguousarray(got).view(np.uint32).reshape(len(rows), 8)
+    np.save(os.path.join(out_dir, "ntt_output_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "ntt_output_u32_limbs.npy"), limbs.astype(np.float64))
 
 
 def timed_events(fn, stream, reps):
@@ -612,7 +649,7 @@ def main():
     big = large_digests()
     parity = {}
     gpu_fwd = None
-    if world == 1:
+    if world == 1 and args.full:
         # Parity of the exact timed path (stark_ntt_dev, device-resident) on the step's input:
         # forward and inverse against the oracle's digests (tests/golden/large_digests.json);
         # the CPU baseline below re-checks the forward output element for element.
@@ -654,6 +691,8 @@ def main():
             def run_steps(k):
                 cyclic_ntt_pipelined(pairs, k, log_total, w_total, ops)
     else:
+        step_input = buf.clone()
+
         def step():
             ctx.ntt_dev(dptr, log_n, 1, w, inverse=False, stream=sptr)
 
@@ -677,6 +716,12 @@ def main():
     settle = int(settle.cpu()[0])
     run_steps(settle - 1)
     torch.cuda.synchronize()
+    if world == 1:
+        # The steps transform the buffer in place and the settle count above depends on the clock, so
+        # the timed steps start from the step's input again: what the last of them leaves depends on
+        # the arguments alone (--dump-outputs).
+        buf.copy_(step_input)
+        del step_input
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -693,6 +738,8 @@ def main():
     elapsed = float(t.cpu()[0])
     ms_per_step = elapsed * 1000.0 / args.steps
     value = world * n * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, buf, n)
 
     extras = dict(parity)
     if not args.no_extras and world == 1:
@@ -867,7 +914,7 @@ def main():
     # launches; achieved = SURVEY 8(d)'s algorithmic 64 B per element per transform (read 32 +
     # write 32) x n / transform time (HIP events on the launch stream).
     ntt_bytes = 64.0 * n
-    if world > 1:
+    if world > 1 and args.full:
         # The distributed step, phase by phase (its own roofline below, nothing from a 1-GPU profile):
         # this rank's local M-point transform, the all-to-all, the cross-rank G-point DFT.
         dphase = distributed_phases(buf, log_total, w_total, ops, stream, on_gloo, local)
@@ -909,7 +956,7 @@ def main():
                 "rocprof_ms_per_transform_avg": round(prof_avg, 4) if prof_avg else None,
                 "rocprof_ms_per_transform_steady_median": round(prof_med, 4) if prof_med else None,
                 "rocprof_kernels": knames, "rocprof_summary": os.path.relpath(PROFILE, ROOT)}
-    if world > 1:
+    if world > 1 and args.full:
         roofline = distributed_roofline(dphase, n, world, log_n, plan, on_gloo)
     if timed:  # the profiled run's kernels over its own timed steps vs that run's ms_per_step
         roofline["rocprof_timed_region_ms_per_transform"] = round(timed["kernel_ms_per_transform"], 4)
@@ -953,6 +1000,9 @@ def main():
         roofline["valu_issue_frac"] = valu["frac"]
     if "power_during_ntt" in extras:
         roofline["power_during_ntt"] = extras["power_during_ntt"]
+    if world > 1 and not args.full:
+        # the N > 1 rooflines are per phase, and the phases take timed runs of their own (--full)
+        roofline = valu = None
 
     cpu = None
     if rank == 0 and world > 1 and not args.no_cpu_baseline:
@@ -1068,7 +1118,7 @@ def main():
                                           "all-to-all)" if world > 1 else ""),
                            "global_batch": 1, "seq_len": n * world, "shard_per_gpu": n,
                            "parallelism": f"distributed NTT x{world} (one all-to-all)" if world > 1 else "single GPU"},
-                "roofline": roofline, "valu_roofline": valu, "cpu_baseline": cpu}
+                "roofline": roofline, "valu_roofline": valu, "cpu_baseline": cpu, "full": args.full}
         line.update(extras)
         print(json.dumps(line), flush=True)
     ctx.close()

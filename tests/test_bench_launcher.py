@@ -40,6 +40,51 @@ def test_single_gpu_runs_in_process():
     assert json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
 
 
+def test_plain_run_leaves_everything_else_to_full(monkeypatch):
+    """A plain run times the headline steps alone; --full turns the extras and the CPU baselines on,
+    and --no-extras / --no-cpu-baseline still take them out of a --full run."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+    a = parsed("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.steps, a.warmup, a.full, a.no_extras, a.no_cpu_baseline) == (7, 2, False, True, True)
+    assert a.dump_outputs is None
+    a = parsed("--full")
+    assert a.full and not a.no_extras and not a.no_cpu_baseline
+    a = parsed("--full", "--no-cpu-baseline", "--dump-outputs", "d")
+    assert a.full and not a.no_extras and a.no_cpu_baseline and a.dump_outputs == "d"
+
+
+def test_dump_outputs_fixed_sample_exact_in_float64(tmp_path):
+    """--dump-outputs: the same rows every time, each row's eight 32-bit limbs exact in float64,
+    well under 64 MB; a small output is written whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 2 * bench.DUMP_ROWS
+    a = np.random.default_rng(7).integers(-2**63, 2**63 - 1, (n, 4), dtype=np.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.from_numpy(a), n)
+    rows = np.load(tmp_path / "a" / "ntt_output_rows.npy")
+    limbs = np.load(tmp_path / "a" / "ntt_output_u32_limbs.npy")
+    assert rows.dtype == limbs.dtype == np.float64
+    assert rows.shape == (bench.DUMP_ROWS,) and limbs.shape == (bench.DUMP_ROWS, 8)
+    assert rows.nbytes + limbs.nbytes <= 64 << 20
+    assert np.all(np.diff(rows) >= 0) and rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "ntt_output_rows.npy"))
+    assert np.array_equal(limbs, np.load(tmp_path / "b" / "ntt_output_u32_limbs.npy"))
+    back = np.ascontiguousarray(limbs.astype(np.uint32)).view(np.int64)
+    assert np.array_equal(back, a[rows.astype(np.int64)])
+    bench.dump_outputs(str(tmp_path / "c"), torch.from_numpy(a[:5].copy()), 5)
+    assert np.array_equal(np.load(tmp_path / "c" / "ntt_output_rows.npy"), np.arange(5.0))
+    small = np.load(tmp_path / "c" / "ntt_output_u32_limbs.npy")
+    assert np.array_equal(small.astype(np.uint32).view(np.int64), a[:5])
+
+
 def test_distributed_roofline_fields():
     """The N > 1 line's roofline (bench.py distributed_roofline): the local kernels' 2 x 64 B per shard
     element against HBM and the all-to-all's (G-1)/G x 32 B per element against G-1 xGMI links, from
