@@ -607,6 +607,22 @@ void fri_proof_json_pieces(const stark_fri_proof* proof, JsonPieces& j) {
   j.text("]");
 }
 
+// serde_json of a StarkProof (utils.rs:122-130; run.rs:549) up to its fri_proof value.
+void stark_proof_json_head(const uint8_t m_root[32], const uint8_t l_root[32], const uint8_t a_root[32],
+                           const BranchSet& main, const BranchSet& lcomb, JsonPieces& j) {
+  j.text("{\"m_root\":");
+  j.bytes(m_root, 32);
+  j.text(",\"l_root\":");
+  j.bytes(l_root, 32);
+  j.text(",\"a_root\":");
+  j.bytes(a_root, 32);
+  j.text(",\"main_branches\":");
+  j.branches(main.leaves, main.leaf_len, main.nodes, main.k, main.depth);
+  j.text(",\"linear_comb_branches\":");
+  j.branches(lcomb.leaves, lcomb.leaf_len, lcomb.nodes, lcomb.k, lcomb.depth);
+  j.text(",\"fri_proof\":");
+}
+
 void fri_proof_json_string(const stark_fri_proof* proof, std::string& o) {
   JsonPieces j;
   fri_proof_json_pieces(proof, j);
@@ -740,17 +756,8 @@ stark_status stark_r1cs_proof_json_from_parts(const uint8_t m_root[32], const ui
   last.last_values = vec(last_values, 32 * n_last);
   fri.layers.push_back(std::move(last));
   JsonPieces j;
-  j.text("{\"m_root\":");
-  j.bytes(m_root, 32);
-  j.text(",\"l_root\":");
-  j.bytes(l_root, 32);
-  j.text(",\"a_root\":");
-  j.bytes(a_root, 32);
-  j.text(",\"main_branches\":");
-  j.branches(ml, mb.leaf_len, mn, mb.k, mb.depth);
-  j.text(",\"linear_comb_branches\":");
-  j.branches(ll, lb.leaf_len, ln, lb.k, lb.depth);
-  j.text(",\"fri_proof\":");
+  stark_proof_json_head(m_root, l_root, a_root, {ml, mb.leaf_len, mn, mb.k, mb.depth},
+                        {ll, lb.leaf_len, ln, lb.k, lb.depth}, j);
   fri_proof_json_pieces(&fri, j);
   j.text("}");
   std::string o;

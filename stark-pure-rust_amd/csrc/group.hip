@@ -543,17 +543,8 @@ void dopen_assemble(DOpen& o, size_t G) {
 // serde_json of the StarkProof (utils.rs:122-130, run.rs:549) from the proof's fields.
 void render_proof(stark_r1cs_proof* p, size_t k_main, size_t k_l) {
   JsonPieces j;
-  j.text("{\"m_root\":");
-  j.bytes(p->m_root, 32);
-  j.text(",\"l_root\":");
-  j.bytes(p->l_root, 32);
-  j.text(",\"a_root\":");
-  j.bytes(p->a_root, 32);
-  j.text(",\"main_branches\":");
-  j.branches(p->m_leaves, 256, p->m_nodes, k_main, p->depth);
-  j.text(",\"linear_comb_branches\":");
-  j.branches(p->l_leaves, 32, p->l_nodes, k_l, p->depth);
-  j.text(",\"fri_proof\":");
+  stark_proof_json_head(p->m_root, p->l_root, p->a_root, {p->m_leaves, 256, p->m_nodes, k_main, p->depth},
+                        {p->l_leaves, 32, p->l_nodes, k_l, p->depth}, j);
   fri_proof_json_pieces(p->fri, j);
   j.text("}");
   j.render(p->json);
@@ -666,12 +657,8 @@ stark_status group_prove(stark_group* g, Begin&& begin, stark_r1cs_proof** out) 
   const size_t skips = kExt;
   std::vector<size_t> positions, aug;
   STARK_TRY(indices(ltree.root(), P, kSpot, (uint32_t)skips, positions));
-  for (size_t j : positions) {
-    aug.push_back(j);
-    aug.push_back((j + P - skips) % P);
-    aug.push_back((j + osteps / 3 * skips) % P);
-    aug.push_back((j + osteps / 3 * 2 * skips) % P);
-  }
+  aug.resize(4 * positions.size());
+  for (size_t i = 0; i < positions.size(); ++i) spot_rows(positions[i], osteps, skips, P, &aug[4 * i]);
   std::vector<DOpen> opens(2 + 2 * layers.size());
   dopen_plan(opens[0], main, aug, G);
   dopen_plan(opens[1], ltree, positions, G);
@@ -1002,7 +989,8 @@ stark_status stark_group_prove_r1cs_bytes(stark_group* g, const uint8_t* r1cs, s
         }
         DevTrace dt;
         STARK_TRY(r1cs_trace_device(c, r1cs, r1cs_len, wtns, wtns_len, &dt, false, &share, r == 0));
-        return dprove_begin_trace(c, G, (uint32_t)r, dt, nullptr, h);
+        STARK_HIP(c, hipStreamSynchronize(c->stream));  // the trace builder runs on the context stream
+        return dprove_open(c, G, (uint32_t)r, dt.view(false), nullptr, nullptr, h);
       },
       out);
   if (share.ev) hipEventDestroy(share.ev);

@@ -331,6 +331,25 @@ struct JsonPieces {
   void prerender(unsigned max_threads = 16);
 };
 void fri_proof_json_pieces(const stark_fri_proof* proof, JsonPieces& j);
+// The StarkProof's text up to and with "fri_proof": (utils.rs:122-130; fri.hip): the three roots and the
+// two sets of openings, which must outlive render().
+struct BranchSet {
+  const std::vector<uint8_t>& leaves;
+  size_t leaf_len;
+  const std::vector<uint8_t>& nodes;
+  size_t k, depth;
+};
+void stark_proof_json_head(const uint8_t m_root[32], const uint8_t l_root[32], const uint8_t a_root[32],
+                           const BranchSet& main, const BranchSet& lcomb, JsonPieces& j);
+
+// The four main-tree rows a spot check at position j opens (prove.rs:337-362, verify.rs:86-118): j, one
+// step back, and the rows one and two thirds of the original steps ahead.
+inline void spot_rows(size_t j, size_t os, size_t skips, size_t prec, size_t out[4]) {
+  out[0] = j;
+  out[1] = (j + prec - skips) % prec;
+  out[2] = (j + os / 3 * skips) % prec;
+  out[3] = (j + os / 3 * 2 * skips) % prec;
+}
 
 }  // namespace stark
 
@@ -375,6 +394,27 @@ struct WtnsHeader {
 stark_status parse_r1cs_header(const uint8_t* r1cs, size_t len, R1csHeader* h);
 stark_status parse_wtns_header(const uint8_t* wtns, size_t len, WtnsHeader* h);
 
+// The trace of one proof as the provers take it (prove.rs:14-26's arguments), whoever holds it: host arrays,
+// a trace builder's columns, or a prepared circuit's with one witness' (r1cs.hip reads it, keeps nothing).
+struct TraceView {
+  // K F0 F1 F2 S P: coefficients, flags, witness and computational trace, os elements of 4 limbs each
+  // (host or device pointers); F0-F2 are null when flag_bytes holds them.
+  const uint64_t* col[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // The flags as 3 x os bytes from a trace builder (calc_flags, run.rs:283-308; flag0 is 1 on every row: the
+  // provers then take F0's shared extension instead of extending it), or null.
+  const uint8_t* flag_bytes = nullptr;
+  const size_t* perm = nullptr;  // permuted_indices, os slots
+  size_t os = 0;
+  const uint64_t* public_wires = nullptr;  // canonical limbs, 4 per wire
+  size_t n_public = 0;
+  const size_t* pfi = nullptr;  // public_first_indices, (wire, slot) pairs
+  size_t n_pfi = 0;
+  size_t n_constraints = 0, n_wires = 0;
+  // Every column, the flag bytes and the permutation are device pointers that the single-GPU prover may
+  // take with its one pack launch (stark_prove_r1cs_bytes only; a prepared circuit's proofs do not pack).
+  bool dev_pack = false;
+};
+
 // The R1CS trace built on the device (r1cs_trace_dev.hip): the host
 // builder's columns (coefficients, witness, computational as canonical
 // elements; flags as bytes; permutation as u64 slots) in ctx->trace_arena,
@@ -387,6 +427,11 @@ struct DevTrace {
   std::vector<uint64_t> public_wires;       // canonical limbs, 4 per wire
   std::vector<size_t> public_first_indices;  // (wire, slot) pairs
   const uint32_t* d_err = nullptr;           // defer_err: the device's wire-id flag, not yet read
+  TraceView view(bool dev_pack) const {
+    return {{(const uint64_t*)coef, nullptr, nullptr, nullptr, (const uint64_t*)wit, (const uint64_t*)comp},
+            flags, (const size_t*)perm, os, public_wires.data(), public_wires.size() / 4,
+            public_first_indices.data(), public_first_indices.size() / 2, n_constraints, n_wires, dev_pack};
+  }
 };
 // A device trace build whose host part (headers, public wires, record walk, the upload of the raw bytes)
 // runs once for several contexts: the producer (a group's member 0) does it all and publishes its
@@ -414,11 +459,6 @@ struct TraceShare {
 stark_status r1cs_trace_device(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* wtns,
                                size_t wtns_len, DevTrace* out, bool defer_err = false, TraceShare* share = nullptr,
                                bool producer = false);
-// mk_r1cs_proof for rank `rank` of `world` on a device trace (r1cs.hip; stark_dprove_begin_bytes' second half).
-stark_status dprove_begin_trace(stark_ctx* ctx, uint32_t world, uint32_t rank, const DevTrace& dt, void* stream,
-                                stark_dprove** out);
-// mk_r1cs_proof on trace columns given as host or device pointers, flags as
-// bytes (r1cs.hip).
 // The witness-independent columns of a circuit: the LDEs of K F0 F1 F2 IDX PIDX and the
 // inverses of Zb2, Zb3 at the points rank + world j (8 x precision/world; K, F0-F2 and the
 // inverses as Montgomery images).  world = 1: the whole domain.  with_zb = false (the verifier,
@@ -427,19 +467,14 @@ stark_status circuit_lde(stark_ctx* ctx, const fe* coef, const uint8_t* flag_byt
                          const size_t* public_first_indices, size_t n_pfi, uint32_t world, uint32_t rank, DevBuf& out,
                          hipStream_t s, bool with_zb = true, const fe** colp = nullptr,
                          uint32_t* spot_log_t = nullptr);
-// mk_r1cs_proof with those columns given (only S, P and A are extended).
-stark_status mk_r1cs_proof_prepared(stark_ctx* ctx, const uint64_t* witness_trace, const uint64_t* computational_trace,
-                                    size_t os, const uint64_t* public_wires, size_t n_public,
-                                    const size_t* public_first_indices, size_t n_pfi, const size_t* permuted_indices,
-                                    const uint64_t* coefficients, const uint8_t* flag_bytes, size_t n_constraints,
-                                    size_t n_wires, const fe* pre, stark_r1cs_proof** out);
-// dprove_begin (r1cs.hip) with a prepared circuit's columns for this rank.
-stark_status dprove_begin_prepared(stark_ctx* ctx, uint32_t world, uint32_t rank, const uint64_t* witness_trace,
-                                   const uint64_t* computational_trace, size_t os, const uint64_t* public_wires,
-                                   size_t n_public, const size_t* public_first_indices, size_t n_pfi,
-                                   const size_t* permuted_indices, const uint64_t* coefficients,
-                                   const uint8_t* flag_bytes, size_t n_constraints, size_t n_wires, const fe* pre,
-                                   void* stream, stark_dprove** out);
+// mk_r1cs_proof on a trace view (r1cs.hip).  pre: null, or a prepared circuit's columns (circuit_lde for
+// world 1; only S, P and A are extended then).
+stark_status mk_r1cs_proof_view(stark_ctx* ctx, const TraceView& v, const fe* pre, stark_r1cs_proof** out);
+// Opens the handle of rank `rank` of `world` on a trace view (r1cs.hip: the rank's share of mk_r1cs_proof up
+// to the constraint rows).  pre: null, or a circuit's columns prepared for this (world, rank).  Columns a
+// builder made on the context stream must be complete (the caller synchronises that stream first).
+stark_status dprove_open(stark_ctx* ctx, uint32_t world, uint32_t rank, const TraceView& v, const fe* pre,
+                         void* stream, stark_dprove** out);
 // A circuit prepared for many proofs (r1cs_trace_dev.hip): everything of a proof that depends on
 // the .r1cs alone.  lde = circuit_lde's columns for (world, rank).
 struct PreparedCircuit;
@@ -467,19 +502,16 @@ struct PreparedCircuit {
   const uint8_t* flags = nullptr;
   const uint64_t* perm = nullptr;
   const uint32_t* slot_wire = nullptr;
+  // the circuit's columns with one witness' (circuit_witness: dt holds wit, comp and the public wires)
+  TraceView view(const DevTrace& dt) const {
+    return {{(const uint64_t*)coef, nullptr, nullptr, nullptr, (const uint64_t*)dt.wit, (const uint64_t*)dt.comp},
+            flags, (const size_t*)perm, os, dt.public_wires.data(), dt.public_wires.size() / 4, pfi.data(),
+            pfi.size() / 2, n_c, n_wires, false};
+  }
 };
 stark_status circuit_build(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len, PreparedCircuit& c);
 // lagrange_interp (fri/src/poly_utils.rs:409-439): coefficients, low degree first (r1cs.hip).
 std::vector<HostFp> lagrange_interp(const std::vector<HostFp>& xs, const std::vector<HostFp>& ys);
-// mk_r1cs_proof with the flags as 3 x os bytes from a trace builder (calc_flags, run.rs:283-308):
-// flag0 must be 1 on every row (the prover then takes F0's shared extension instead of extending it).
-stark_status mk_r1cs_proof_bytes_flags(stark_ctx* ctx, const uint64_t* witness_trace,
-                                      const uint64_t* computational_trace, size_t os, const uint64_t* public_wires,
-                                      size_t n_public, const size_t* public_first_indices, size_t n_pfi,
-                                      const size_t* permuted_indices, const uint64_t* coefficients,
-                                      const uint8_t* flag_bytes, size_t n_constraints, size_t n_wires,
-                                      stark_r1cs_proof** out, bool dev_in = false);
-
 // FRI prover on device values (fri.hip).  fri_enqueue puts every layer on the
 // context stream with a device-side transcript and queues the roots' download;
 // after the caller's stream synchronisation, fri_finish samples the indices

@@ -846,11 +846,6 @@ static stark_status coset_lde(stark_ctx* ctx, fe* coef, uint32_t batch, fe* out,
   return ntt_device_from(ctx, coef, log_p - log_steps, out, log_p, batch, tw_h, false, s);
 }
 
-static stark_status lde(stark_ctx* ctx, fe* coef, uint32_t batch, fe* out, uint32_t log_steps, uint32_t log_prec,
-                        const Twiddles& tw_g1_inv, const Twiddles& tw_g2, hipStream_t s) {
-  return coset_lde(ctx, coef, batch, out, log_steps, log_prec, 0, 0, tw_g1_inv, tw_g2, tw_g2, s);
-}
-
 // tag 0: IDX[i] = i; tag > 0: F0[i] = 1 for i < tag (calc_flags' flag0, run.rs:283-308), 0 after.
 __global__ void const_column_kernel(fe* __restrict__ out, uint64_t n, uint64_t tag) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1118,259 +1113,392 @@ static std::vector<fe> boundary_consts(const HostFp& g2, uint64_t prec, uint64_t
   return h;
 }
 
-static stark_status prove_r1cs(stark_ctx* ctx, const uint64_t* witness_trace, const uint64_t* computational_trace,
-                               size_t os, const uint64_t* public_wires, size_t n_public,
-                               const size_t* public_first_indices, size_t n_pfi, const size_t* permuted_indices,
-                               const uint64_t* coefficients, const uint64_t* flag0, const uint64_t* flag1,
-                               const uint64_t* flag2, const uint8_t* flag_bytes, size_t n_constraints, size_t n_wires,
-                               stark_r1cs_proof** out, const fe* pre = nullptr, bool dev_in = false) {
-  // dev_in: every column, the flag bytes and the permutation are device pointers (one pack launch).
-  // pre != nullptr: the circuit's LDE columns K F0 F1 F2 IDX PIDX (precision each) and the
-  // inverses of Zb2, Zb3 (2 x precision), prepared once per circuit (stark_r1cs_circuit_new);
-  // only S, P and A are extended here.
-  PhaseClock clk("mk_r1cs_proof");
-  const FieldHost& F = FieldHost::get();
-  hipStream_t s = ctx->stream;
-  // prove.rs:30-53
-  if (os > 3 * n_constraints * n_wires || os % 3 != 0) return STARK_ERR_BAD_ARG;
-  if (os < 5) return STARK_ERR_BAD_LENGTH;  // the reference's steps/log_steps disagree below 8 steps
-  const uint32_t log_steps = log2_ceil_ref(os - 1);
-  const uint32_t log_prec = log_steps + kLogExtensionFactor;
+// ---- the constraint stage ---------------------------------------------------------------------------
+//
+// What a proof runs up to its constraint rows, on one GPU (prove_r1cs: the whole domain, log_g = rank = 0)
+// or as one rank of a world (dprove_begin: the points rank + 2^log_g j).  Both hosts call the steps below
+// in the same order; where they differ on purpose (streams, trees, arenas, how Zb is inverted) the
+// difference is an argument of a step or stays in the host.
+
+struct StageDims {
+  uint32_t log_steps = 0, log_prec = 0, log_g = 0, rank = 0;
+  uint64_t os = 0, steps = 0, prec = 0, skips = 0;
+  uint64_t P = 0;  // this host's points: prec >> log_g
+};
+
+// prove.rs:30-53's argument checks and the sizes they give.
+static stark_status stage_dims(const TraceView& v, uint32_t world, uint32_t rank, StageDims& d) {
+  if (world == 0 || world > (uint32_t)kExtensionFactor || (world & (world - 1)) || rank >= world)
+    return STARK_ERR_BAD_ARG;
+  if (v.os > 3 * v.n_constraints * v.n_wires || v.os % 3 != 0) return STARK_ERR_BAD_ARG;
+  if (v.os < 5) return STARK_ERR_BAD_LENGTH;  // the reference's steps/log_steps disagree below 8 steps
+  d.log_steps = log2_ceil_ref(v.os - 1);
+  d.log_prec = d.log_steps + kLogExtensionFactor;
   // get_pseudorandom_indices(_, precision, ...) asserts precision < 2^24 (fri/src/utils.rs:88), first reached
   // when r is derived (utils.rs:279); the reference cannot prove larger traces.
-  if (log_prec >= 24) return STARK_ERR_BAD_LENGTH;
-  const uint64_t steps = (uint64_t)1 << log_steps, prec = (uint64_t)1 << log_prec;
-  const uint64_t skips = prec / steps;
-  for (size_t i = 0; i < n_pfi; ++i)
-    if (public_first_indices[2 * i] >= n_public || public_first_indices[2 * i + 1] >= steps) return STARK_ERR_BAD_ARG;
+  if (d.log_prec >= 24) return STARK_ERR_BAD_LENGTH;
+  d.log_g = 0;
+  while ((1u << d.log_g) < world) ++d.log_g;
+  d.rank = rank;
+  d.os = v.os;
+  d.steps = (uint64_t)1 << d.log_steps;
+  d.prec = (uint64_t)1 << d.log_prec;
+  d.skips = d.prec / d.steps;
+  d.P = d.prec >> d.log_g;
+  for (size_t i = 0; i < v.n_pfi; ++i)
+    if (v.pfi[2 * i] >= v.n_public || v.pfi[2 * i + 1] >= d.steps) return STARK_ERR_BAD_ARG;
+  return STARK_OK;
+}
 
-  // Roots (prove.rs:71-94): g2 = 7^((p-1)/precision), g1 = g2^8.
-  ProofRoots roots;
-  STARK_TRY(proof_roots(ctx, log_steps, log_prec, 1, roots));
-  const HostFp g2 = roots.g2;
-  const uint64_t* g2c = roots.g2c;
-  const Twiddles* tw2 = roots.tw2;
-  const Twiddles* tw1i = roots.tw1i;
-  const Mont mc = mont();
-  // The shared size-only columns (prepared circuits carry their own): IDX's extension; F0's whenever
-  // the flags are the trace builder's (flag bytes, calc_flags run.rs:283-308: 1 on the os rows), so only
-  // K F1 F2 S P PIDX are extended here; 1 / Zb3; and the table that gives 1 / Zb2 by partial fractions,
-  // so the proof has no batch inverse over the domain at all (zb2_partial_fractions).
+// One proof's working set up to the constraint rows.
+struct Stage {
+  StageDims d;
+  ProofRoots roots;  // twh = tw2 on one GPU (h = g2)
+  Mont mc;
+  // The shared size-only columns (prepared circuits carry their own): IDX's extension; F0's whenever the
+  // flags are a trace builder's (flag bytes, calc_flags run.rs:283-308: 1 on the os rows), so only
+  // K F1 F2 S P PIDX are extended; 1 / Zb3; and the table that gives 1 / Zb2 by partial fractions
+  // (ca.tinv), so the proof has no batch inverse over the domain at all (zb2_partial_fractions).
   SharedCols sc;
-  if (!pre)
-    STARK_TRY(shared_columns(ctx, flag_bytes != nullptr, os, log_steps, log_prec, 0, 0, *tw1i, *tw2, *tw2, s, sc));
-  const fe *idx_ext = sc.idx, *f0_ext = sc.f0, *izb3 = sc.izb3;
   ConstraintArgs ca;
-  ca.tinv = nullptr;
-  if (sc.tinv && izb3 && zb2_partial_fractions(g2, prec, skips, 0, public_first_indices, n_pfi, ca)) ca.tinv = sc.tinv;
-
-  fe *raw, *wcopy, *cols, *nmr, *dnm, *tot, *dnm_c, *inv_dnm, *zb, *inv_zb, *consts, *rows, *lvals;
-  uint64_t* perm;
-  uint64_t* acc_leaves;
-  Transcript* d_tr;
-  const uint32_t nb = (uint32_t)((steps + kScanBlock - 1) / kScanBlock);
-  Carve cv;
-  cv.add(&raw, 7 * steps);  // K F0 F1 F2 S P PIDX (then A's coefficients reuse K's slot)
-  cv.add(&wcopy, steps);
-  cv.add(&perm, steps);
-  cv.add(&acc_leaves, 5 * steps);
-  cv.add(&cols, 8 * prec);  // the extensions of K F0 F1 F2 S P PIDX A (IDX's is shared: idx_ext)
-  cv.add(&nmr, steps);
-  cv.add(&dnm, steps);
-  cv.add(&tot, 2 * (size_t)nb);
-  cv.add(&dnm_c, steps);
-  cv.add(&inv_dnm, steps);
-  cv.add(&zb, 2 * prec);
-  cv.add(&inv_zb, 2 * prec);
-  cv.add(&consts, 2 * n_pfi + 2);
-  cv.add(&rows, 8 * prec);
-  cv.add(&lvals, prec);
-  cv.add(&d_tr, 1);
-  STARK_TRY(cv.commit(ctx, ctx->r1cs_arena));
-
-  // Interpolants and boundary points (utils.rs:421-474), host side (#pub points).
   HostFp x_last;
-  // alive until the proof's final synchronisation
-  const std::vector<fe> h = boundary_consts(g2, prec, skips, public_wires, public_first_indices, n_pfi, &x_last);
-  {  // through pinned slot 4 (an asynchronous copy; a pageable one blocks the host)
-    uint8_t* pin = nullptr;
-    STARK_TRY(ctx_pinned(ctx, 4, kPinned4ConstsOff + h.size() * sizeof(fe), (void**)&pin));
-    memcpy(pin + kPinned4ConstsOff, h.data(), h.size() * sizeof(fe));
-    STARK_HIP(ctx, hipMemcpyAsync(consts, pin + kPinned4ConstsOff, h.size() * sizeof(fe), hipMemcpyHostToDevice, s));
-  }
-  // Upload the six value columns, zero tails (prove.rs:59-69; inv_best_fft pads the flags).  The
-  // inputs may be host or device pointers (the device trace builder's columns): hipMemcpyDefault.
-  const uint64_t* src[6] = {coefficients, flag0, flag1, flag2, witness_trace, computational_trace};
-  const bool pack = dev_in && !pre;
-  if (pack) {
-    if (!flag_bytes && (!flag0 || !flag1 || !flag2)) return STARK_ERR_BAD_ARG;
-    PackArgs pa;
-    for (int c = 0; c < 6; ++c) pa.col[c] = (const fe*)src[c];
-    pa.fb = flag_bytes;
-    pa.perm_in = (const uint64_t*)permuted_indices;
-    pa.os = os;
-    pa.steps = steps;
-    pa.raw = raw;
-    pa.wcopy = wcopy;
-    pa.perm = perm;
-    static_assert(sizeof(Transcript) % 4 == 0, "transcript words");
-    pa.tr = (uint32_t*)d_tr;
-    pa.tr_words = (uint32_t)(sizeof(Transcript) / 4);
-    pa.k_slot = f0_ext ? 1 : 0;
-    hipLaunchKernelGGL(r1cs_pack_kernel, dim3(blocks_for(std::max<uint64_t>(steps, pa.tr_words))), dim3(256), 0, s,
-                       pa);
-    STARK_HIP(ctx, hipGetLastError());
-  }
-  for (int c = pre ? 4 : 0; c < 6 && !pack; ++c) {
-    if (!(flag_bytes && c >= 1 && c <= 3))
-      STARK_HIP(ctx, hipMemcpyAsync(raw + c * steps, src[c], os * sizeof(fe), hipMemcpyDefault, s));
+  std::vector<fe> consts_h;  // boundary_consts: alive until the host's synchronisation behind their upload
+  fe *raw, *wcopy, *cols, *nmr, *dnm, *tot, *dnm_c, *inv_dnm, *zb, *inv_zb, *consts, *rows, *lvals;
+  uint64_t *perm, *acc_leaves;
+  Transcript* d_tr;
+  uint32_t nb;     // the scans' blocks
+  InvPlan inv_d;   // the batch inverse of A's denominators
+};
+
+static stark_status stage_begin(stark_ctx* ctx, const TraceView& v, const fe* pre, uint32_t world, uint32_t rank,
+                                hipStream_t s, Stage& st) {
+  STARK_TRY(stage_dims(v, world, rank, st.d));
+  const StageDims& d = st.d;
+  // Roots (prove.rs:71-94): g2 = 7^((p-1)/precision), g1 = g2^8; h = g2^world generates a rank's coset.
+  STARK_TRY(proof_roots(ctx, d.log_steps, d.log_prec, world, st.roots));
+  st.mc = mont();
+  if (!pre)
+    STARK_TRY(shared_columns(ctx, v.flag_bytes != nullptr, d.os, d.log_steps, d.log_prec, d.log_g, d.rank,
+                             *st.roots.tw1i, *st.roots.tw2, *st.roots.twh, s, st.sc));
+  st.ca.tinv = nullptr;
+  if (st.sc.tinv && st.sc.izb3 &&
+      zb2_partial_fractions(st.roots.g2, d.prec, d.skips, d.log_g, v.pfi, v.n_pfi, st.ca))
+    st.ca.tinv = st.sc.tinv;
+  return STARK_OK;
+}
+
+// The working set carved out of the host's arena (zb also stages the flag bytes: zb_count elements), and
+// the interpolants and boundary points (utils.rs:421-474), host side (#pub points).
+static stark_status stage_buffers(stark_ctx* ctx, const TraceView& v, Stage& st, size_t zb_count, DevBuf& arena) {
+  const uint64_t steps = st.d.steps, P = st.d.P;
+  st.nb = (uint32_t)((steps + kScanBlock - 1) / kScanBlock);
+  Carve cv;
+  cv.add(&st.raw, 7 * steps);  // K F0 F1 F2 S P PIDX (then A's coefficients reuse K's slot)
+  cv.add(&st.wcopy, steps);
+  cv.add(&st.perm, steps);
+  cv.add(&st.acc_leaves, 5 * steps);
+  cv.add(&st.cols, 8 * P);  // the extensions of K F0 F1 F2 S P PIDX A (IDX's is shared: sc.idx)
+  cv.add(&st.nmr, steps);
+  cv.add(&st.dnm, steps);
+  cv.add(&st.tot, 2 * (size_t)st.nb);
+  cv.add(&st.dnm_c, steps);
+  cv.add(&st.inv_dnm, steps);
+  cv.add(&st.zb, zb_count);
+  cv.add(&st.inv_zb, 2 * P);
+  cv.add(&st.consts, 2 * v.n_pfi + 2);
+  cv.add(&st.rows, 8 * P);
+  cv.add(&st.lvals, P);
+  cv.add(&st.d_tr, 1);
+  STARK_TRY(cv.commit(ctx, arena));
+  st.consts_h = boundary_consts(st.roots.g2, st.d.prec, st.d.skips, v.public_wires, v.pfi, v.n_pfi, &st.x_last);
+  return STARK_OK;
+}
+
+// The step columns with zero tails (prove.rs:59-69; inv_best_fft pads the flags), host or device sources
+// (hipMemcpyDefault), 0/1 flag bytes widened on the GPU; K moved into F0's slot when F0's extension is
+// shared (the six extended columns are then contiguous from slot 1); the permutation, the witness copy
+// and the transcript's zero fill.
+static stark_status stage_uploads(stark_ctx* ctx, const TraceView& v, const fe* pre, const Stage& st, hipStream_t s) {
+  const uint64_t steps = st.d.steps, os = st.d.os;
+  fe* const raw = st.raw;
+  for (int c = pre ? 4 : 0; c < 6; ++c) {
+    if (!(v.flag_bytes && c >= 1 && c <= 3))
+      STARK_HIP(ctx, hipMemcpyAsync(raw + c * steps, v.col[c], os * sizeof(fe), hipMemcpyDefault, s));
     if (steps > os) STARK_HIP(ctx, hipMemsetAsync(raw + c * steps + os, 0, (steps - os) * sizeof(fe), s));
   }
-  if (flag_bytes && !pre && !pack) {  // 0/1 flags as bytes (the trace builder's compact form), widened on the GPU
-    uint8_t* d_fb = (uint8_t*)zb;  // zb is free until the Zb kernel
-    STARK_HIP(ctx, hipMemcpyAsync(d_fb, flag_bytes, 3 * os, hipMemcpyDefault, s));
-    hipLaunchKernelGGL(r1cs_flags_kernel, dim3(blocks_for(3 * os)), dim3(256), 0, s, (const uint8_t*)d_fb,
-                       (uint64_t)os, steps, raw + steps);
+  if (v.flag_bytes && !pre) {
+    uint8_t* d_fb = (uint8_t*)st.zb;  // zb is free until the Zb kernel
+    STARK_HIP(ctx, hipMemcpyAsync(d_fb, v.flag_bytes, 3 * os, hipMemcpyDefault, s));
+    hipLaunchKernelGGL(r1cs_flags_kernel, dim3(blocks_for(3 * os)), dim3(256), 0, s, (const uint8_t*)d_fb, os, steps,
+                       raw + steps);
     STARK_HIP(ctx, hipGetLastError());
   }
   static_assert(sizeof(size_t) == sizeof(uint64_t), "size_t is 64-bit");
-  if (!pack) {
-    if (f0_ext)  // K into F0's slot: the six extended columns are contiguous from slot 1
-      STARK_HIP(ctx, hipMemcpyAsync(raw + steps, raw, steps * sizeof(fe), hipMemcpyDeviceToDevice, s));
-    STARK_HIP(ctx, hipMemcpyAsync(perm, permuted_indices, os * sizeof(uint64_t), hipMemcpyDefault, s));
-    STARK_HIP(ctx, hipMemcpyAsync(wcopy, raw + 4 * steps, steps * sizeof(fe), hipMemcpyDeviceToDevice, s));
-    STARK_HIP(ctx, hipMemsetAsync(d_tr, 0, sizeof(Transcript), s));
+  if (st.sc.f0) STARK_HIP(ctx, hipMemcpyAsync(raw + steps, raw, steps * sizeof(fe), hipMemcpyDeviceToDevice, s));
+  STARK_HIP(ctx, hipMemcpyAsync(st.perm, v.perm, os * sizeof(uint64_t), hipMemcpyDefault, s));
+  STARK_HIP(ctx, hipMemcpyAsync(st.wcopy, raw + 4 * steps, steps * sizeof(fe), hipMemcpyDeviceToDevice, s));
+  STARK_HIP(ctx, hipMemsetAsync(st.d_tr, 0, sizeof(Transcript), s));
+  return STARK_OK;
+}
+
+// The same as one launch, when every source is a device pointer (TraceView::dev_pack, one GPU only).
+static stark_status stage_pack(stark_ctx* ctx, const TraceView& v, const Stage& st, hipStream_t s) {
+  if (!v.flag_bytes && (!v.col[1] || !v.col[2] || !v.col[3])) return STARK_ERR_BAD_ARG;
+  PackArgs pa;
+  for (int c = 0; c < 6; ++c) pa.col[c] = (const fe*)v.col[c];
+  pa.fb = v.flag_bytes;
+  pa.perm_in = (const uint64_t*)v.perm;
+  pa.os = st.d.os;
+  pa.steps = st.d.steps;
+  pa.raw = st.raw;
+  pa.wcopy = st.wcopy;
+  pa.perm = st.perm;
+  static_assert(sizeof(Transcript) % 4 == 0, "transcript words");
+  pa.tr = (uint32_t*)st.d_tr;
+  pa.tr_words = (uint32_t)(sizeof(Transcript) / 4);
+  pa.k_slot = st.sc.f0 ? 1 : 0;
+  hipLaunchKernelGGL(r1cs_pack_kernel, dim3(blocks_for(std::max<uint64_t>(st.d.steps, pa.tr_words))), dim3(256), 0, s,
+                     pa);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
+// PIDX's step column (slot 6; IDX is not materialised: sc.idx is its shared extension) and the accumulator
+// tree -> a_root (utils.rs:250-270).  acc_dig non-null (merkle_level0): the index kernel hashes each 40-B
+// leaf as it writes it, and the tree is built from those digests.
+static stark_status stage_accumulator(stark_ctx* ctx, const Stage& st, stark_merkle_tree* acc_tree, uint32_t* acc_dig,
+                                      hipStream_t s) {
+  const uint64_t steps = st.d.steps;
+  hipLaunchKernelGGL(r1cs_index_kernel, dim3(blocks_for(steps)), dim3(256), 0, s, (const uint64_t*)st.perm, st.d.os,
+                     steps, (const fe*)st.wcopy, st.raw + 6 * steps, st.acc_leaves, acc_dig);
+  STARK_HIP(ctx, hipGetLastError());
+  return merkle_build(ctx, acc_tree, (const uint8_t*)st.acc_leaves, steps, 40, s, 0, acc_dig != nullptr);
+}
+
+// The context's second stream and its event, created on first use.
+static stark_status aux_stream(stark_ctx* ctx) {
+  if (!ctx->ev_aux) STARK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
+  if (!ctx->aux) STARK_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
+  return STARK_OK;
+}
+
+// A (utils.rs:293-339, prove.rs:183-184): r from a_root (utils.rs:272-290), the running products of the
+// numerators and denominators over the steps, their batch inverse (whose top level is the proof's one
+// mid-pipeline host round trip) and A = nmr / dnm.  It reads the trace and a_root only (IDX and PIDX at
+// the step points are i and the permutation), so on sa = the aux stream it runs beside the main LDE,
+// which the host enqueues between the two halves; on sa = s it runs in line.
+// The enqueue half: up to the scans, and io2's guard taken for sa (it covers the pinned top arrays too:
+// multi_inv_device on another stream uses both).  The host then enqueues the denominators' multi_inv_up
+// on sa with the scratch of its choice.
+static stark_status a_chain_enqueue(stark_ctx* ctx, Stage& st, stark_merkle_tree* acc_tree, hipStream_t s,
+                                    hipStream_t sa) {
+  const uint64_t steps = st.d.steps;
+  if (sa != s) {
+    STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, s));  // the trace columns, the transcript's zero fill, a_root
+    STARK_HIP(ctx, hipStreamWaitEvent(sa, ctx->ev_aux, 0));
   }
+  hipLaunchKernelGGL(r1cs_r_kernel, dim3(1), dim3(64), 0, sa, (const uint32_t*)merkle_root_dev(acc_tree),
+                     (uint32_t)(st.d.prec - 1), st.mc.r2, pow32(), st.d_tr);
+  STARK_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(r1cs_a_vals_kernel, dim3(blocks_for(steps)), dim3(256), 0, sa, (const fe*)nullptr,
+                     (const fe*)nullptr, (const uint64_t*)st.perm, st.d.os, (const fe*)st.wcopy, steps,
+                     (const Transcript*)st.d_tr, st.mc.r2, st.nmr, st.dnm);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(product_scan(ctx, ScanArrays{{st.nmr, st.dnm}, {st.tot, st.tot + st.nb}, {nullptr, st.dnm_c}}, 2, steps,
+                         st.mc, sa));
+  return buf_acquire(ctx, ctx->io2, sa);
+}
+
+static stark_status a_denominators_up(stark_ctx* ctx, Stage& st, hipStream_t sa, DevBuf& scratch) {
+  fe* const top_d = multi_inv_h_top(ctx, 0);
+  if (!top_d) return STARK_ERR_OOM;
+  return multi_inv_up(ctx, st.dnm_c, st.inv_dnm, st.d.steps, sa, scratch, top_d, st.inv_d);
+}
+
+// Which step columns are extended here, into their slots of cols.
+static stark_status extend_columns(stark_ctx* ctx, const Stage& st, fe* coef, uint32_t batch, fe* out, hipStream_t s) {
+  return coset_lde(ctx, coef, batch, out, st.d.log_steps, st.d.log_prec, st.d.log_g, st.d.rank, *st.roots.tw1i,
+                   *st.roots.tw2, *st.roots.twh, s);
+}
+static stark_status extend_trace(stark_ctx* ctx, const Stage& st, const fe* pre, hipStream_t s) {
+  const uint64_t steps = st.d.steps, P = st.d.P;
+  if (pre)  // S and P only: K, the flags, IDX and PIDX are the circuit's
+    return extend_columns(ctx, st, st.raw + 4 * steps, 2, st.cols + 4 * P, s);
+  if (st.sc.f0)  // K (in F0's slot) F1 F2 S P PIDX
+    return extend_columns(ctx, st, st.raw + steps, 6, st.cols + P, s);
+  return extend_columns(ctx, st, st.raw, 7, st.cols, s);  // K F0 F1 F2 S P PIDX
+}
+
+// The finish half: the host round trip (shared_top: a second batch inverse whose up pass the host enqueued,
+// so that both top levels are inverted behind this one synchronisation), the denominators' down pass,
+// A = nmr / dnm into dnm (free after its scan's canonical copy; raw may still be read by the LDE), s
+// joined behind sa, and A's extension in slot 7.
+static stark_status a_chain_finish(stark_ctx* ctx, Stage& st, hipStream_t s, hipStream_t sa,
+                                   const InvPlan* shared_top = nullptr) {
+  const uint64_t steps = st.d.steps;
+  STARK_HIP(ctx, hipStreamSynchronize(sa));
+  multi_inv_top(st.inv_d);
+  if (shared_top) multi_inv_top(*shared_top);
+  STARK_TRY(multi_inv_down(ctx, st.inv_d, sa));
+  hipLaunchKernelGGL(r1cs_a_mini_kernel, dim3(blocks_for(steps)), dim3(256), 0, sa, (const fe*)st.nmr,
+                     (const fe*)st.inv_dnm, steps, st.dnm);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(buf_release(ctx, ctx->io2, sa));
+  if (sa != s) {
+    STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, sa));
+    STARK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_aux, 0));
+  }
+  return extend_columns(ctx, st, st.dnm, 1, st.cols + 7 * st.d.P, s);
+}
+
+// Zb2 = prod_k (x - x_k), Zb3 = x - x_last at this host's points (utils.rs:438-474) into zb, for a proof
+// that has no table of their inverses; *count = how many values the host then inverts (Zb2's, and Zb3's
+// unless 1 / Zb3 is the shared column).
+static stark_status zb_enqueue(stark_ctx* ctx, const Stage& st, size_t n_pfi, hipStream_t s, uint64_t* count) {
+  const Twiddles* tw2 = st.roots.tw2;
+  const uint64_t P = st.d.P;
+  hipLaunchKernelGGL(r1cs_zb_kernel, dim3(blocks_for(P)), dim3(256), 0, s, tw2->d_lo, tw2->d_hi, tw2->kb, P,
+                     (uint64_t)st.d.rank, st.d.log_g, (const fe*)st.consts, (uint32_t)n_pfi, to_dev(st.x_last),
+                     st.mc.rinv, st.mc.one, st.zb, st.sc.izb3 ? nullptr : st.zb + P);
+  STARK_HIP(ctx, hipGetLastError());
+  *count = st.sc.izb3 ? P : 2 * P;
+  return STARK_OK;
+}
+
+// The constraint kernel's arguments and their tables (upload_constraint_tables).  plane: the rows'
+// layout (ConstraintArgs::rows).  The shifts are multiples of 8, hence of 2^log_g.
+static stark_status constraint_args(stark_ctx* ctx, const TraceView& v, const fe* pre, Stage& st, uint64_t plane,
+                                    hipStream_t s) {
+  const StageDims& d = st.d;
+  const uint64_t P = d.P;
+  const Twiddles* tw2 = st.roots.tw2;
+  ConstraintArgs& ca = st.ca;
+  for (int c = 0; c < 6; ++c) ca.col[c] = st.cols + (size_t)c * P;
+  ca.col[6] = pre ? pre + 4 * P : st.sc.idx;
+  ca.col[7] = pre ? pre + 5 * P : st.cols + 6 * P;
+  ca.col[8] = st.cols + 7 * P;  // A
+  if (st.sc.f0) {
+    ca.col[0] = st.cols + P;  // K
+    ca.col[1] = st.sc.f0;
+  }
+  if (pre)
+    for (int c = 0; c < 4; ++c) ca.col[c] = pre + (size_t)c * P;
+  ca.inv_zb = pre ? pre + 6 * P : st.inv_zb;
+  ca.inv_zb3 = st.sc.izb3 ? st.sc.izb3 : ca.inv_zb + P;
+  ca.interp2 = st.consts + v.n_pfi;
+  ca.interp3 = st.consts + 2 * v.n_pfi;
+  ca.lo = tw2->d_lo;
+  ca.hi = tw2->d_hi;
+  ca.rows = st.rows;
+  ca.plane = plane;
+  ca.err = &st.d_tr->err;
+  ca.prec = P;
+  ca.shift1 = ((d.os / 3 * d.skips) % d.prec) >> d.log_g;
+  ca.shift2 = ((d.os / 3 * 2 * d.skips) % d.prec) >> d.log_g;
+  ca.back = d.skips >> d.log_g;
+  ca.g_add = d.rank;
+  ca.log_g = d.log_g;
+  ca.log_prec = d.log_prec;
+  ca.kb = tw2->kb;
+  ca.n2 = (uint32_t)v.n_pfi;
+  ca.n3 = 1;
+  ca.tr = st.d_tr;
+  set_inv_z(ca, st.roots.g2, d.steps);
+  ca.mont_cols = pre ? 1 : 0;
+  return upload_constraint_tables(ctx, st.d_tr, ca, s);
+}
+
+static stark_status constraint_launch(stark_ctx* ctx, const Stage& st, hipStream_t s) {
+  hipLaunchKernelGGL(r1cs_constraint_kernel, dim3(blocks_for(st.d.P)), dim3(256), 0, s, st.ca);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
+// The eight powers of g2^steps (the k kernel's xs table).
+static XsPowers xs_powers(const HostFp& g2, uint64_t steps) {
+  const FieldHost& F = FieldHost::get();
+  XsPowers xs;
+  const HostFp w8 = F.pow_u64(g2, steps);
+  HostFp wt = F.one();
+  for (int t = 0; t < 8; ++t) {
+    xs.v[t] = to_dev(wt);
+    wt = F.mul(wt, w8);
+  }
+  return xs;
+}
+
+// Transcript::err (the constraint kernel's flags) as a call's status and message.
+static stark_status transcript_status(stark_ctx* ctx, int err) {
+  if (!err) return STARK_OK;
+  ctx->last_error = (err & 1) ? "invalid D: Q does not vanish where Z does (utils.rs:379-418)"
+                              : "invalid B: boundary value mismatch (utils.rs:477-524)";
+  return STARK_ERR_CHECK;
+}
+
+// pre != nullptr: the circuit's LDE columns K F0 F1 F2 IDX PIDX (precision each) and the inverses of
+// Zb2, Zb3 (2 x precision), prepared once per circuit (stark_r1cs_circuit_new); only S, P and A are
+// extended here.
+static stark_status prove_r1cs(stark_ctx* ctx, const TraceView& v, const fe* pre, stark_r1cs_proof** out) {
+  PhaseClock clk("mk_r1cs_proof");
+  hipStream_t s = ctx->stream;
+  Stage st;
+  STARK_TRY(stage_begin(ctx, v, pre, 1, 0, s, st));
+  const uint32_t log_prec = st.d.log_prec;
+  const uint64_t os = st.d.os, prec = st.d.prec, skips = st.d.skips;
+  const Mont& mc = st.mc;
+  STARK_TRY(stage_buffers(ctx, v, st, 2 * prec, ctx->r1cs_arena));
+  fe* const rows = st.rows;
+  fe* const lvals = st.lvals;
+  Transcript* const d_tr = st.d_tr;
+  {  // the boundary constants through pinned slot 4 (an asynchronous copy; a pageable one blocks the host)
+    const std::vector<fe>& h = st.consts_h;
+    uint8_t* pin = nullptr;
+    STARK_TRY(ctx_pinned(ctx, 4, kPinned4ConstsOff + h.size() * sizeof(fe), (void**)&pin));
+    memcpy(pin + kPinned4ConstsOff, h.data(), h.size() * sizeof(fe));
+    STARK_HIP(ctx, hipMemcpyAsync(st.consts, pin + kPinned4ConstsOff, h.size() * sizeof(fe), hipMemcpyHostToDevice, s));
+  }
+  if (v.dev_pack && !pre) STARK_TRY(stage_pack(ctx, v, st, s));
+  else STARK_TRY(stage_uploads(ctx, v, pre, st, s));
   clk.mark("setup + uploads enqueued");
   auto proof = std::make_unique<stark_r1cs_proof>();
-  // Accumulator tree -> a_root (utils.rs:250-270) -> r (utils.rs:272-290): the index kernel hashes each
-  // 40-B leaf as it writes it (level 0).
+  // The trees are the context's; the index, constraint and linear-combination kernels hash level 0.
   stark_merkle_tree *acc_tree, *m_tree, *l_tree;
   STARK_TRY(ctx_tree(ctx, 2, &acc_tree));
   STARK_TRY(ctx_tree(ctx, 3, &m_tree));
   STARK_TRY(ctx_tree(ctx, 4, &l_tree));
   uint32_t* acc_dig = nullptr;
-  STARK_TRY(merkle_level0(ctx, acc_tree, steps, s, &acc_dig));
-  // (IDX is not materialised: idx_ext is the shared extension.)
-  hipLaunchKernelGGL(r1cs_index_kernel, dim3(blocks_for(steps)), dim3(256), 0, s, (const uint64_t*)perm,
-                     (uint64_t)os, steps, (const fe*)wcopy, raw + 6 * steps, acc_leaves, acc_dig);
-  STARK_HIP(ctx, hipGetLastError());
-  STARK_TRY(merkle_build(ctx, acc_tree, (const uint8_t*)acc_leaves, steps, 40, s, 0, true));
-  // A (utils.rs:293-339, prove.rs:183-184): r from a_root, the running products of the numerators and
-  // denominators over the steps, their batch inverse (whose top level is the proof's one mid-pipeline host
-  // round trip) and A = nmr / dnm.  It reads the trace and a_root only (IDX and PIDX at the step points
-  // are i and the permutation), so when no Zb inverse shares its round trip it runs on the aux stream
-  // beside the main LDE, which the host enqueues before it waits.
-  const bool a_aside = pre || ca.tinv;
-  if (!ctx->ev_aux) STARK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
-  if (!ctx->aux) STARK_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-  hipStream_t sa = s;
-  if (a_aside) {
-    sa = ctx->aux;
-    STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, s));  // the trace columns, the transcript's zero fill, a_root
-    STARK_HIP(ctx, hipStreamWaitEvent(sa, ctx->ev_aux, 0));
-  }
-  hipLaunchKernelGGL(r1cs_r_kernel, dim3(1), dim3(64), 0, sa, (const uint32_t*)merkle_root_dev(acc_tree),
-                     (uint32_t)(prec - 1), mc.r2, pow32(), d_tr);
-  STARK_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(r1cs_a_vals_kernel, dim3(blocks_for(steps)), dim3(256), 0, sa, (const fe*)nullptr,
-                     (const fe*)nullptr, (const uint64_t*)perm, (uint64_t)os, (const fe*)wcopy, steps,
-                     (const Transcript*)d_tr, mc.r2, nmr, dnm);
-  STARK_HIP(ctx, hipGetLastError());
-  STARK_TRY(product_scan(ctx, ScanArrays{{nmr, dnm}, {tot, tot + nb}, {nullptr, dnm_c}}, 2, steps, mc, sa));
-  // The cold proof's two batch inverses (the A denominators over the steps; Zb2, Zb3 over the precision
-  // domain, which prepared circuits carry) share one host round trip: both up passes, one
+  STARK_TRY(merkle_level0(ctx, acc_tree, st.d.steps, s, &acc_dig));
+  STARK_TRY(stage_accumulator(ctx, st, acc_tree, acc_dig, s));
+  // The A chain runs on the aux stream when no Zb inverse shares its round trip.  Otherwise (the cold proof
+  // without the partial-fraction table) it runs in line, and the two batch inverses (the A denominators over
+  // the steps; Zb2, Zb3 over the precision domain) share one host round trip: both up passes, one
   // synchronisation, both top levels on the host, then the down passes.
-  InvPlan inv_d, inv_z;
-  fe* const top_d = multi_inv_h_top(ctx, 0);
-  fe* const top_z = multi_inv_h_top(ctx, 1);
-  if (!top_d || !top_z) return STARK_ERR_OOM;
-  // (io2's guard covers the pinned top arrays too: multi_inv_device on another stream uses both)
-  STARK_TRY(buf_acquire(ctx, ctx->io2, sa));
-  if (!pre && !ca.tinv) {
-    hipLaunchKernelGGL(r1cs_zb_kernel, dim3(blocks_for(prec)), dim3(256), 0, s, tw2->d_lo, tw2->d_hi, tw2->kb, prec,
-                       (uint64_t)0, (uint32_t)0, (const fe*)consts, (uint32_t)n_pfi, to_dev(x_last), mc.rinv, mc.one,
-                       zb, izb3 ? nullptr : zb + prec);
-    STARK_HIP(ctx, hipGetLastError());
-    STARK_TRY(multi_inv_up(ctx, zb, inv_zb, izb3 ? prec : 2 * prec, s, ctx->io2, top_z, inv_z));
+  const bool a_aside = pre || st.ca.tinv;
+  STARK_TRY(aux_stream(ctx));
+  const hipStream_t sa = a_aside ? ctx->aux : s;
+  STARK_TRY(a_chain_enqueue(ctx, st, acc_tree, s, sa));
+  InvPlan inv_z;
+  if (!a_aside) {
+    fe* const top_z = multi_inv_h_top(ctx, 1);
+    if (!top_z) return STARK_ERR_OOM;
+    uint64_t n_zb = 0;
+    STARK_TRY(zb_enqueue(ctx, st, v.n_pfi, s, &n_zb));
+    STARK_TRY(multi_inv_up(ctx, st.zb, st.inv_zb, n_zb, s, ctx->io2, top_z, inv_z));
   }
-  STARK_TRY(multi_inv_up(ctx, dnm_c, inv_dnm, steps, sa, ctx->inv_tmp, top_d, inv_d));
-  if (pre)  // S and P only: K, the flags, IDX and PIDX are the circuit's
-    STARK_TRY(lde(ctx, raw + 4 * steps, 2, cols + 4 * prec, log_steps, log_prec, *tw1i, *tw2, s));
-  else if (f0_ext)  // K (in F0's slot) F1 F2 S P PIDX
-    STARK_TRY(lde(ctx, raw + steps, 6, cols + prec, log_steps, log_prec, *tw1i, *tw2, s));
-  else  // K F0 F1 F2 S P PIDX
-    STARK_TRY(lde(ctx, raw, 7, cols, log_steps, log_prec, *tw1i, *tw2, s));
-  STARK_HIP(ctx, hipStreamSynchronize(sa));
-  multi_inv_top(inv_d);
-  multi_inv_top(inv_z);
-  STARK_TRY(multi_inv_down(ctx, inv_d, sa));
-  // A = nmr / dnm into dnm (free after its scan's canonical copy)
-  hipLaunchKernelGGL(r1cs_a_mini_kernel, dim3(blocks_for(steps)), dim3(256), 0, sa, (const fe*)nmr,
-                     (const fe*)inv_dnm, steps, dnm);
-  STARK_HIP(ctx, hipGetLastError());
-  STARK_TRY(buf_release(ctx, ctx->io2, sa));
-  if (a_aside) {
-    STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, sa));
-    STARK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_aux, 0));
-  }
-  STARK_TRY(lde(ctx, dnm, 1, cols + 7 * prec, log_steps, log_prec, *tw1i, *tw2, s));  // A in slot 7
-  STARK_TRY(multi_inv_down(ctx, inv_z, s));  // (empty plan with a prepared circuit)
-  const fe* ext_idx = pre ? pre + 4 * prec : idx_ext;
-  const fe* ext_pidx = pre ? pre + 5 * prec : cols + 6 * prec;
-
-  // Constraint kernel.
-  for (int c = 0; c < 6; ++c) ca.col[c] = cols + (size_t)c * prec;
-  ca.col[6] = ext_idx;
-  ca.col[8] = cols + 7 * prec;  // A
-  ca.col[7] = ext_pidx;
-  if (f0_ext) {
-    ca.col[0] = cols + prec;  // K
-    ca.col[1] = f0_ext;
-  }
-  if (pre)
-    for (int c = 0; c < 4; ++c) ca.col[c] = pre + (size_t)c * prec;
-  ca.inv_zb = pre ? pre + 6 * prec : inv_zb;
-  ca.inv_zb3 = izb3 ? izb3 : ca.inv_zb + prec;
-  ca.interp2 = consts + n_pfi;
-  ca.interp3 = consts + 2 * n_pfi;
-  ca.lo = tw2->d_lo;
-  ca.hi = tw2->d_hi;
-  ca.rows = rows;
-  ca.plane = prec;  // column-major: coalesced stores here and loads in the L kernel and the main tree
-  ca.err = &d_tr->err;
-  ca.prec = prec;
-  ca.shift1 = (os / 3 * skips) % prec;
-  ca.shift2 = (os / 3 * 2 * skips) % prec;
-  ca.back = skips;
-  ca.g_add = 0;
-  ca.log_g = 0;
-  ca.log_prec = log_prec;
-  ca.kb = tw2->kb;
-  ca.n2 = (uint32_t)n_pfi;
-  ca.n3 = 1;
-  ca.tr = d_tr;
-  set_inv_z(ca, g2, steps);
-  ca.mont_cols = pre ? 1 : 0;
-  STARK_TRY(upload_constraint_tables(ctx, d_tr, ca, s));
+  STARK_TRY(a_denominators_up(ctx, st, sa, ctx->inv_tmp));
+  STARK_TRY(extend_trace(ctx, st, pre, s));
+  STARK_TRY(a_chain_finish(ctx, st, s, sa, &inv_z));
+  STARK_TRY(multi_inv_down(ctx, inv_z, s));  // (empty plan when the A chain ran aside)
+  // plane = prec, column-major rows: coalesced stores here and loads in the L kernel and the main tree
+  STARK_TRY(constraint_args(ctx, v, pre, st, prec, s));
   // Main tree over the 256-B rows (prove.rs:261-264): the constraint kernel hashes each row as it makes it
   // (level 0), the tree's levels above are built from those digests; the proofs open the rows as 8 planes.
-  STARK_TRY(merkle_level0(ctx, m_tree, prec, s, &ca.leaf));
-  hipLaunchKernelGGL(r1cs_constraint_kernel, dim3(blocks_for(prec)), dim3(256), 0, s, ca);
-  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(merkle_level0(ctx, m_tree, prec, s, &st.ca.leaf));
+  STARK_TRY(constraint_launch(ctx, st, s));
   STARK_TRY(merkle_build(ctx, m_tree, (const uint8_t*)rows, prec, 256, s, prec * sizeof(fe), true));
-  {
-    XsPowers xs;
-    const HostFp w8 = F.pow_u64(g2, steps);
-    HostFp wt = F.one();
-    for (int t = 0; t < 8; ++t) {
-      xs.v[t] = to_dev(wt);
-      wt = F.mul(wt, w8);
-    }
-    hipLaunchKernelGGL(r1cs_k_kernel, dim3(1), dim3(kKThreads), 0, s, (const uint32_t*)merkle_root_dev(m_tree),
-                       mc.r2, mc.one, xs, pow32(), d_tr);
-    STARK_HIP(ctx, hipGetLastError());
-  }
+  hipLaunchKernelGGL(r1cs_k_kernel, dim3(1), dim3(kKThreads), 0, s, (const uint32_t*)merkle_root_dev(m_tree), mc.r2,
+                     mc.one, xs_powers(st.roots.g2, st.d.steps), pow32(), d_tr);
+  STARK_HIP(ctx, hipGetLastError());
   LincombArgs la;
   la.rows = rows;
   la.plane = prec;
@@ -1403,14 +1531,12 @@ static stark_status prove_r1cs(stark_ctx* ctx, const uint64_t* witness_trace, co
   uint32_t* h_trace_err = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(h_tr) + kPinned1TraceErrOff);
   STARK_HIP(ctx, hipMemcpyAsync(h_tr, d_tr, kTrHead, hipMemcpyDeviceToHost, s));
   if (ctx->trace_err) STARK_HIP(ctx, hipMemcpyAsync(h_trace_err, ctx->trace_err, 4, hipMemcpyDeviceToHost, s));
-  if (!ctx->ev_aux) STARK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
-  if (!ctx->aux) STARK_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
   STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, s));
 
   // prove_low_degree(L, g2, precision / 4, skips) on the resident L (prove.rs:367), enqueued behind the rest.
   FriPendingPtr fri_pending;
   clk.mark("prover kernels enqueued");
-  STARK_TRY(fri_enqueue(ctx, (const fe*)lvals, prec, g2c, prec / 4, (uint32_t)skips, &fri_pending, l_tree,
+  STARK_TRY(fri_enqueue(ctx, (const fe*)lvals, prec, st.roots.g2c, prec / 4, (uint32_t)skips, &fri_pending, l_tree,
                         l_rf.made));
   clk.mark("FRI kernels enqueued");
   // While the FRI layers run: the roots, the spot checks (prove.rs:337-362), their openings (gathered on
@@ -1424,9 +1550,7 @@ static stark_status prove_r1cs(stark_ctx* ctx, const uint64_t* witness_trace, co
   }
   if (h_tr->err) {
     hipStreamSynchronize(s);  // (the enqueued FRI work finishes before the proof is dropped)
-    ctx->last_error = (h_tr->err & 1) ? "invalid D: Q does not vanish where Z does (utils.rs:379-418)"
-                                      : "invalid B: boundary value mismatch (utils.rs:477-524)";
-    return STARK_ERR_CHECK;
+    return transcript_status(ctx, h_tr->err);
   }
   memcpy(proof->a_root, h_tr->roots[0], 32);
   memcpy(proof->m_root, h_tr->roots[1], 32);
@@ -1435,12 +1559,8 @@ static stark_status prove_r1cs(stark_ctx* ctx, const uint64_t* witness_trace, co
   STARK_TRY(stark_get_pseudorandom_indices(proof->l_root, 32, (uint32_t)prec, kSpotChecks, (uint32_t)skips, pos32));
   std::vector<size_t> positions(kSpotChecks), aug(4 * kSpotChecks);
   for (int i = 0; i < kSpotChecks; ++i) {
-    const size_t j = pos32[i];
-    positions[i] = j;
-    aug[4 * i] = j;
-    aug[4 * i + 1] = (j + prec - skips) % prec;
-    aug[4 * i + 2] = (j + os / 3 * skips) % prec;
-    aug[4 * i + 3] = (j + os / 3 * 2 * skips) % prec;
+    positions[i] = pos32[i];
+    spot_rows(pos32[i], os, skips, prec, &aug[4 * i]);
   }
   std::vector<uint8_t> l_leaves(32 * kSpotChecks), l_nodes(32 * kSpotChecks * log_prec);
   std::vector<uint8_t> m_leaves(256 * 4 * kSpotChecks), m_nodes(32 * 4 * kSpotChecks * log_prec);
@@ -1452,17 +1572,9 @@ static stark_status prove_r1cs(stark_ctx* ctx, const uint64_t* witness_trace, co
   }
   // StarkProof JSON (utils.rs:122-130; run.rs:549 serde_json::to_string), its head rendered now.
   JsonPieces j;
-  j.text("{\"m_root\":");
-  j.bytes(proof->m_root, 32);
-  j.text(",\"l_root\":");
-  j.bytes(proof->l_root, 32);
-  j.text(",\"a_root\":");
-  j.bytes(proof->a_root, 32);
-  j.text(",\"main_branches\":");
-  j.branches(m_leaves, 256, m_nodes, 4 * kSpotChecks, log_prec);
-  j.text(",\"linear_comb_branches\":");
-  j.branches(l_leaves, 32, l_nodes, kSpotChecks, log_prec);
-  j.text(",\"fri_proof\":");
+  stark_proof_json_head(proof->m_root, proof->l_root, proof->a_root,
+                        {m_leaves, 256, m_nodes, (size_t)4 * kSpotChecks, log_prec},
+                        {l_leaves, 32, l_nodes, (size_t)kSpotChecks, log_prec}, j);
   clk.mark("spot-check openings");
   std::vector<GatherReq> extra;
   stark_fri_proof* fri = nullptr;
@@ -1470,11 +1582,11 @@ static stark_status prove_r1cs(stark_ctx* ctx, const uint64_t* witness_trace, co
     // The head renders on the side thread while this one waits for the FRI layers and gathers their
     // openings (for a small proof the FRI kernels finish before the head would be rendered).
     HostTask head([&] { j.prerender(16); });
-    const stark_status st = fri_finish(ctx, fri_pending.get(), extra, &fri);
+    const stark_status fst = fri_finish(ctx, fri_pending.get(), extra, &fri);
     clk.mark("FRI wait + indices + gather");
     head.wait();
     clk.mark("proof head JSON (beside them)");
-    if (st != STARK_OK) return st;
+    if (fst != STARK_OK) return fst;
   }
   proof->fri = fri;  // owned by the proof from here on
   fri_proof_json_pieces(fri, j);
@@ -1772,33 +1884,11 @@ stark_status circuit_spot_values(stark_ctx* ctx, const PreparedCircuit& c, const
   return STARK_OK;
 }
 
-stark_status mk_r1cs_proof_prepared(stark_ctx* ctx, const uint64_t* witness_trace, const uint64_t* computational_trace,
-                                    size_t os, const uint64_t* public_wires, size_t n_public,
-                                    const size_t* public_first_indices, size_t n_pfi, const size_t* permuted_indices,
-                                    const uint64_t* coefficients, const uint8_t* flag_bytes, size_t n_constraints,
-                                    size_t n_wires, const fe* pre, stark_r1cs_proof** out) {
-  if (!ctx || !out || !pre) return STARK_ERR_BAD_ARG;
-  *out = nullptr;
-  STARK_HIP(ctx, hipSetDevice(ctx->device));
-  const stark_status st = prove_r1cs(ctx, witness_trace, computational_trace, os, public_wires, n_public,
-                                     public_first_indices, n_pfi, permuted_indices, coefficients, nullptr, nullptr,
-                                     nullptr, flag_bytes, n_constraints, n_wires, out, pre);
-  hipStreamSynchronize(ctx->stream);
-  return st;
-}
-
-stark_status mk_r1cs_proof_bytes_flags(stark_ctx* ctx, const uint64_t* witness_trace,
-                                      const uint64_t* computational_trace, size_t os, const uint64_t* public_wires,
-                                      size_t n_public, const size_t* public_first_indices, size_t n_pfi,
-                                      const size_t* permuted_indices, const uint64_t* coefficients,
-                                      const uint8_t* flag_bytes, size_t n_constraints, size_t n_wires,
-                                      stark_r1cs_proof** out, bool dev_in) {
+stark_status mk_r1cs_proof_view(stark_ctx* ctx, const TraceView& v, const fe* pre, stark_r1cs_proof** out) {
   if (!ctx || !out) return STARK_ERR_BAD_ARG;
   *out = nullptr;
   STARK_HIP(ctx, hipSetDevice(ctx->device));
-  const stark_status st = prove_r1cs(ctx, witness_trace, computational_trace, os, public_wires, n_public,
-                                     public_first_indices, n_pfi, permuted_indices, coefficients, nullptr, nullptr,
-                                     nullptr, flag_bytes, n_constraints, n_wires, out, nullptr, dev_in);
+  const stark_status st = prove_r1cs(ctx, v, pre, out);
   hipStreamSynchronize(ctx->stream);
   return st;
 }
@@ -1821,15 +1911,13 @@ stark_status mk_r1cs_proof_bytes_flags(stark_ctx* ctx, const uint64_t* witness_t
 struct DProveState {
   stark_ctx* ctx = nullptr;
   hipStream_t s = nullptr;
-  uint32_t G = 1, r = 0, log_g = 0;
-  uint64_t steps = 0, prec = 0, P = 0, skips = 0, os = 0;
-  uint32_t log_steps = 0, log_prec = 0;
+  StageDims dim;
   uint64_t g2c[4];
   DevBuf arena;
   stark_merkle_tree* acc_tree = nullptr;
   fe *rows = nullptr, *lvals = nullptr;
   Transcript* d_tr = nullptr;
-  fe xs_m[8];
+  XsPowers xs;
 };
 
 }  // namespace stark
@@ -1844,207 +1932,43 @@ struct stark_dprove {
 
 namespace stark {
 
-// Coset LDE of `batch` step columns (coef, destroyed) into out (batch x P).
-static stark_status lde_coset(DProveState& d, fe* coef, uint32_t batch, fe* out, const Twiddles& tw_g1_inv,
-                              const Twiddles& tw_g2, const Twiddles& tw_h) {
-  return coset_lde(d.ctx, coef, batch, out, d.log_steps, d.log_prec, d.log_g, d.r, tw_g1_inv, tw_g2, tw_h, d.s);
-}
-
-static stark_status dprove_begin(stark_ctx* ctx, uint32_t world, uint32_t rank, const uint64_t* witness_trace,
-                                 const uint64_t* computational_trace, size_t os, const uint64_t* public_wires,
-                                 size_t n_public, const size_t* public_first_indices, size_t n_pfi,
-                                 const size_t* permuted_indices, const uint64_t* coefficients, const uint64_t* flag0,
-                                 const uint64_t* flag1, const uint64_t* flag2, const uint8_t* flag_bytes,
-                                 size_t n_constraints, size_t n_wires, hipStream_t s, stark_dprove* h,
-                                 const fe* pre = nullptr) {
-  // pre != nullptr: this rank's prepared circuit columns (circuit_lde with world, rank): the coset
-  // LDEs of K F0 F1 F2 IDX PIDX and the Zb inverses; only S, P and A are extended here.
-  const FieldHost& F = FieldHost::get();
+// pre != nullptr: this rank's prepared circuit columns (circuit_lde with world, rank): the coset LDEs of
+// K F0 F1 F2 IDX PIDX and the Zb inverses; only S, P and A are extended here.
+static stark_status dprove_begin(stark_ctx* ctx, uint32_t world, uint32_t rank, const TraceView& v, const fe* pre,
+                                 hipStream_t s, stark_dprove* h) {
   DProveState& d = h->st;
-  if (world == 0 || world > (uint32_t)kExtensionFactor || (world & (world - 1)) || rank >= world)
-    return STARK_ERR_BAD_ARG;
-  // prove.rs:30-53 (as prove_r1cs)
-  if (os > 3 * n_constraints * n_wires || os % 3 != 0) return STARK_ERR_BAD_ARG;
-  if (os < 5) return STARK_ERR_BAD_LENGTH;
-  const uint32_t log_steps = log2_ceil_ref(os - 1);
-  const uint32_t log_prec = log_steps + kLogExtensionFactor;
-  if (log_prec >= 24) return STARK_ERR_BAD_LENGTH;
+  Stage st;
+  STARK_TRY(stage_begin(ctx, v, pre, world, rank, s, st));
   d.ctx = ctx;
   d.s = s;
-  d.G = world;
-  d.r = rank;
-  while ((1u << d.log_g) < world) ++d.log_g;
-  d.log_steps = log_steps;
-  d.log_prec = log_prec;
-  d.steps = (uint64_t)1 << log_steps;
-  d.prec = (uint64_t)1 << log_prec;
-  d.P = d.prec >> d.log_g;
-  d.skips = d.prec / d.steps;
-  d.os = os;
-  const uint64_t steps = d.steps, prec = d.prec, P = d.P, skips = d.skips;
-  for (size_t i = 0; i < n_pfi; ++i)
-    if (public_first_indices[2 * i] >= n_public || public_first_indices[2 * i + 1] >= steps) return STARK_ERR_BAD_ARG;
-
-  // Roots (prove.rs:71-94); h = g2^G generates this rank's coset of size P.
-  ProofRoots roots;
-  STARK_TRY(proof_roots(ctx, log_steps, log_prec, world, roots));
-  const HostFp g2 = roots.g2;
-  memcpy(d.g2c, roots.g2c, 32);
-  const Twiddles *tw2 = roots.tw2, *tw1i = roots.tw1i, *twh = roots.twh;
-  const Mont mc = mont();
-  // This rank's share of the shared size-only columns, as in prove_r1cs.
-  SharedCols sc;
-  if (!pre)
-    STARK_TRY(shared_columns(ctx, flag_bytes != nullptr, os, log_steps, log_prec, d.log_g, rank, *tw1i, *tw2, *twh, s,
-                             sc));
-  const fe *idx_ext = sc.idx, *f0_ext = sc.f0, *izb3 = sc.izb3;
-  ConstraintArgs ca;
-  ca.tinv = nullptr;
-  if (sc.tinv && izb3 && zb2_partial_fractions(g2, prec, skips, d.log_g, public_first_indices, n_pfi, ca))
-    ca.tinv = sc.tinv;
-
-  fe *raw, *wcopy, *cols, *nmr, *dnm, *tot, *dnm_c, *inv_dnm, *zb, *inv_zb, *consts;
-  uint64_t* perm;
-  uint64_t* acc_leaves;
-  const uint32_t nb = (uint32_t)((steps + kScanBlock - 1) / kScanBlock);
-  Carve cv;
-  cv.add(&raw, 7 * steps);  // K F0 F1 F2 S P PIDX
-  cv.add(&wcopy, steps);
-  cv.add(&perm, steps);
-  cv.add(&acc_leaves, 5 * steps);
-  cv.add(&cols, 8 * P);  // K F0 F1 F2 S P PIDX A (IDX's extension is shared: idx_ext)
-  cv.add(&nmr, steps);
-  cv.add(&dnm, steps);
-  cv.add(&tot, 2 * (size_t)nb);
-  cv.add(&dnm_c, steps);
-  cv.add(&inv_dnm, steps);
-  cv.add(&zb, 2 * P > 3 * os / 32 + 1 ? 2 * P : 3 * os / 32 + 1);
-  cv.add(&inv_zb, 2 * P);
-  cv.add(&consts, 2 * n_pfi + 2);
-  cv.add(&d.rows, 8 * P);
-  cv.add(&d.lvals, P);
-  cv.add(&d.d_tr, 1);
-  STARK_TRY(cv.commit(ctx, d.arena));
-
-  // Interpolants and boundary points (utils.rs:421-474).
-  HostFp x_last;
-  const std::vector<fe> hc2 = boundary_consts(g2, prec, skips, public_wires, public_first_indices, n_pfi, &x_last);
-  STARK_HIP(ctx, hipMemcpyAsync(consts, hc2.data(), hc2.size() * sizeof(fe), hipMemcpyHostToDevice, s));
-  // Step columns (prove.rs:59-69), host or device sources.
-  const uint64_t* src[6] = {coefficients, flag0, flag1, flag2, witness_trace, computational_trace};
-  for (int c = pre ? 4 : 0; c < 6; ++c) {
-    if (!(flag_bytes && c >= 1 && c <= 3))
-      STARK_HIP(ctx, hipMemcpyAsync(raw + c * steps, src[c], os * sizeof(fe), hipMemcpyDefault, s));
-    if (steps > os) STARK_HIP(ctx, hipMemsetAsync(raw + c * steps + os, 0, (steps - os) * sizeof(fe), s));
-  }
-  if (flag_bytes && !pre) {
-    uint8_t* d_fb = (uint8_t*)zb;  // zb is free until the Zb kernel (sized for the 3 os flag bytes)
-    STARK_HIP(ctx, hipMemcpyAsync(d_fb, flag_bytes, 3 * os, hipMemcpyDefault, s));
-    hipLaunchKernelGGL(r1cs_flags_kernel, dim3(blocks_for(3 * os)), dim3(256), 0, s, (const uint8_t*)d_fb,
-                       (uint64_t)os, steps, raw + steps);
-    STARK_HIP(ctx, hipGetLastError());
-  }
-  if (f0_ext)  // K into F0's slot: the six extended columns are contiguous from slot 1
-    STARK_HIP(ctx, hipMemcpyAsync(raw + steps, raw, steps * sizeof(fe), hipMemcpyDeviceToDevice, s));
-  STARK_HIP(ctx, hipMemcpyAsync(perm, permuted_indices, os * sizeof(uint64_t), hipMemcpyDefault, s));
-  STARK_HIP(ctx, hipMemcpyAsync(wcopy, raw + 4 * steps, steps * sizeof(fe), hipMemcpyDeviceToDevice, s));
-  STARK_HIP(ctx, hipMemsetAsync(d.d_tr, 0, sizeof(Transcript), s));
-  // (PIDX in slot 6; IDX is not materialised: idx_ext)
-  hipLaunchKernelGGL(r1cs_index_kernel, dim3(blocks_for(steps)), dim3(256), 0, s, (const uint64_t*)perm,
-                     (uint64_t)os, steps, (const fe*)wcopy, raw + 6 * steps, acc_leaves, (uint32_t*)nullptr);
-  STARK_HIP(ctx, hipGetLastError());
-  // Accumulator tree -> a_root -> r (utils.rs:250-290), on every rank.
+  d.dim = st.d;
+  memcpy(d.g2c, st.roots.g2c, 32);
+  d.xs = xs_powers(st.roots.g2, st.d.steps);
+  // The handle owns its arena (zb is sized for the 3 os flag bytes too) and its accumulator tree.
+  STARK_TRY(stage_buffers(ctx, v, st, std::max<uint64_t>(2 * st.d.P, 3 * st.d.os / 32 + 1), d.arena));
+  d.rows = st.rows;
+  d.lvals = st.lvals;
+  d.d_tr = st.d_tr;
+  STARK_HIP(ctx, hipMemcpyAsync(st.consts, st.consts_h.data(), st.consts_h.size() * sizeof(fe), hipMemcpyHostToDevice,
+                                s));
+  STARK_TRY(stage_uploads(ctx, v, pre, st, s));
   STARK_TRY(stark_merkle_new(ctx, &d.acc_tree));
-  STARK_TRY(merkle_build(ctx, d.acc_tree, (const uint8_t*)acc_leaves, steps, 40, s));
-  // A (utils.rs:293-339): step-domain scans on every rank, then this rank's coset.  As on one GPU, the
-  // chain (r, the scans, their batch inverse with its host round trip, A = nmr / dnm) runs on the
-  // context's aux stream beside the coset LDE, which the host enqueues before it waits.
-  if (!ctx->ev_aux) STARK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_aux, hipEventDisableTiming));
-  if (!ctx->aux) STARK_HIP(ctx, hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking));
-  hipStream_t sa = ctx->aux;
-  STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, s));  // the trace columns, the transcript's zero fill, a_root
-  STARK_HIP(ctx, hipStreamWaitEvent(sa, ctx->ev_aux, 0));
-  hipLaunchKernelGGL(r1cs_r_kernel, dim3(1), dim3(64), 0, sa, (const uint32_t*)merkle_root_dev(d.acc_tree),
-                     (uint32_t)(prec - 1), mc.r2, pow32(), d.d_tr);
-  STARK_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(r1cs_a_vals_kernel, dim3(blocks_for(steps)), dim3(256), 0, sa, (const fe*)nullptr,
-                     (const fe*)nullptr, (const uint64_t*)perm, (uint64_t)os, (const fe*)wcopy, steps,
-                     (const Transcript*)d.d_tr, mc.r2, nmr, dnm);
-  STARK_HIP(ctx, hipGetLastError());
-  STARK_TRY(product_scan(ctx, ScanArrays{{nmr, dnm}, {tot, tot + nb}, {nullptr, dnm_c}}, 2, steps, mc, sa));
-  InvPlan inv_d;
-  fe* const top_d = multi_inv_h_top(ctx, 0);
-  if (!top_d) return STARK_ERR_OOM;
-  STARK_TRY(buf_acquire(ctx, ctx->io2, sa));  // (io2's guard covers the pinned top arrays too)
-  STARK_TRY(multi_inv_up(ctx, dnm_c, inv_dnm, steps, sa, ctx->io2, top_d, inv_d));
-  if (pre)
-    STARK_TRY(lde_coset(d, raw + 4 * steps, 2, cols + 4 * P, *tw1i, *tw2, *twh));
-  else if (f0_ext)  // K (in F0's slot) F1 F2 S P PIDX
-    STARK_TRY(lde_coset(d, raw + steps, 6, cols + P, *tw1i, *tw2, *twh));
-  else  // K F0 F1 F2 S P PIDX
-    STARK_TRY(lde_coset(d, raw, 7, cols, *tw1i, *tw2, *twh));
-  STARK_HIP(ctx, hipStreamSynchronize(sa));
-  multi_inv_top(inv_d);
-  STARK_TRY(multi_inv_down(ctx, inv_d, sa));
-  // A = nmr / dnm into dnm (free after its scan's canonical copy; raw may still be read by the LDE)
-  hipLaunchKernelGGL(r1cs_a_mini_kernel, dim3(blocks_for(steps)), dim3(256), 0, sa, (const fe*)nmr,
-                     (const fe*)inv_dnm, steps, dnm);
-  STARK_HIP(ctx, hipGetLastError());
-  STARK_TRY(buf_release(ctx, ctx->io2, sa));
-  STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, sa));
-  STARK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_aux, 0));
-  STARK_TRY(lde_coset(d, dnm, 1, cols + 7 * P, *tw1i, *tw2, *twh));  // A in slot 7
-  if (!pre && !ca.tinv) {  // Zb2 / Zb3 at this rank's points and their inverses
-    hipLaunchKernelGGL(r1cs_zb_kernel, dim3(blocks_for(P)), dim3(256), 0, s, tw2->d_lo, tw2->d_hi, tw2->kb, P,
-                       (uint64_t)rank, d.log_g, (const fe*)consts, (uint32_t)n_pfi, to_dev(x_last), mc.rinv, mc.one,
-                       zb, izb3 ? nullptr : zb + P);
-    STARK_HIP(ctx, hipGetLastError());
-    STARK_TRY(multi_inv_device(ctx, zb, inv_zb, izb3 ? P : 2 * P, s));
+  STARK_TRY(stage_accumulator(ctx, st, d.acc_tree, nullptr, s));  // on every rank
+  // The step-domain A chain is repeated on every rank, on the context's aux stream beside the coset LDE.
+  STARK_TRY(aux_stream(ctx));
+  const hipStream_t sa = ctx->aux;
+  STARK_TRY(a_chain_enqueue(ctx, st, d.acc_tree, s, sa));
+  STARK_TRY(a_denominators_up(ctx, st, sa, ctx->io2));
+  STARK_TRY(extend_trace(ctx, st, pre, s));
+  STARK_TRY(a_chain_finish(ctx, st, s, sa));
+  if (!pre && !st.ca.tinv) {  // Zb2 / Zb3 at this rank's points and their inverses
+    uint64_t n_zb = 0;
+    STARK_TRY(zb_enqueue(ctx, st, v.n_pfi, s, &n_zb));
+    STARK_TRY(multi_inv_device(ctx, st.zb, st.inv_zb, n_zb, s));
   }
-  for (int c = 0; c < 6; ++c) ca.col[c] = cols + (size_t)c * P;
-  ca.col[8] = cols + 7 * P;  // A
-  ca.inv_zb = pre ? pre + 6 * P : inv_zb;
-  ca.inv_zb3 = izb3 ? izb3 : ca.inv_zb + P;
-  ca.col[6] = pre ? pre + 4 * P : idx_ext;
-  ca.col[7] = pre ? pre + 5 * P : cols + 6 * P;
-  if (f0_ext) {
-    ca.col[0] = cols + P;  // K
-    ca.col[1] = f0_ext;
-  }
-  if (pre)
-    for (int c = 0; c < 4; ++c) ca.col[c] = pre + (size_t)c * P;
-  ca.interp2 = consts + n_pfi;
-  ca.interp3 = consts + 2 * n_pfi;
-  ca.lo = tw2->d_lo;
-  ca.hi = tw2->d_hi;
-  ca.rows = d.rows;
-  ca.plane = 0;  // the distributed prover exports its rows (stark_dprove_rows)
-  ca.err = &d.d_tr->err;
-  ca.prec = P;
-  ca.shift1 = ((os / 3 * skips) % prec) >> d.log_g;  // multiples of 8, hence of G
-  ca.shift2 = ((os / 3 * 2 * skips) % prec) >> d.log_g;
-  ca.back = skips >> d.log_g;
-  ca.g_add = rank;
-  ca.log_g = d.log_g;
-  ca.log_prec = log_prec;
-  ca.kb = tw2->kb;
-  ca.n2 = (uint32_t)n_pfi;
-  ca.n3 = 1;
-  ca.tr = d.d_tr;
-  set_inv_z(ca, g2, steps);
-  ca.mont_cols = pre ? 1 : 0;
-  {
-    const HostFp w8 = F.pow_u64(g2, steps);
-    HostFp wt = F.one();
-    for (int t = 0; t < 8; ++t) {
-      d.xs_m[t] = to_dev(wt);
-      wt = F.mul(wt, w8);
-    }
-  }
-  STARK_TRY(upload_constraint_tables(ctx, d.d_tr, ca, s));
-  hipLaunchKernelGGL(r1cs_constraint_kernel, dim3(blocks_for(P)), dim3(256), 0, s, ca);
-  STARK_HIP(ctx, hipGetLastError());
-  // hc2 and the uploads above must outlive the copies: wait here (the caller
+  STARK_TRY(constraint_args(ctx, v, pre, st, 0, s));  // plane = 0: the rank exports its rows (stark_dprove_rows)
+  STARK_TRY(constraint_launch(ctx, st, s));
+  // consts_h and the uploads above must outlive the copies: wait here (the caller
   // reads a_root and the constraint flags next anyway).
   STARK_HIP(ctx, hipStreamSynchronize(s));
   return STARK_OK;
@@ -2056,6 +1980,12 @@ using namespace stark;
 
 extern "C" {
 
+// The host-array entry points' check (the flags as field elements): an array is null while its length is not 0.
+static bool host_trace_null(const TraceView& v) {
+  if (v.os && (!v.col[0] || !v.col[1] || !v.col[2] || !v.col[3] || !v.col[4] || !v.col[5] || !v.perm)) return true;
+  return (v.n_public && !v.public_wires) || (v.n_pfi && !v.pfi);
+}
+
 stark_status stark_mk_r1cs_proof(stark_ctx* ctx, const uint64_t* witness_trace, const uint64_t* computational_trace,
                                  size_t original_steps, const uint64_t* public_wires, size_t n_public,
                                  const size_t* public_first_indices, size_t n_public_first,
@@ -2064,16 +1994,11 @@ stark_status stark_mk_r1cs_proof(stark_ctx* ctx, const uint64_t* witness_trace, 
                                  stark_r1cs_proof** out) {
   if (!ctx || !out) return STARK_ERR_BAD_ARG;
   *out = nullptr;
-  if (original_steps && (!witness_trace || !computational_trace || !permuted_indices || !coefficients || !flag0 ||
-                         !flag1 || !flag2))
-    return STARK_ERR_BAD_ARG;
-  if ((n_public && !public_wires) || (n_public_first && !public_first_indices)) return STARK_ERR_BAD_ARG;
-  STARK_HIP(ctx, hipSetDevice(ctx->device));
-  const stark_status st = prove_r1cs(ctx, witness_trace, computational_trace, original_steps, public_wires, n_public,
-                                     public_first_indices, n_public_first, permuted_indices, coefficients, flag0,
-                                     flag1, flag2, nullptr, n_constraints, n_wires, out);
-  hipStreamSynchronize(ctx->stream);
-  return st;
+  const TraceView v{{coefficients, flag0, flag1, flag2, witness_trace, computational_trace}, nullptr,
+                    permuted_indices, original_steps, public_wires, n_public, public_first_indices, n_public_first,
+                    n_constraints, n_wires, false};
+  if (host_trace_null(v)) return STARK_ERR_BAD_ARG;
+  return mk_r1cs_proof_view(ctx, v, nullptr, out);
 }
 
 stark_status stark_r1cs_proof_json(const stark_r1cs_proof* proof, char* buf, size_t cap, size_t* len) {
@@ -2132,49 +2057,12 @@ stark_status stark_dprove_begin(stark_ctx* ctx, uint32_t world, uint32_t rank, c
                                 size_t n_constraints, size_t n_wires, void* stream, stark_dprove** out) {
   if (!ctx || !out) return STARK_ERR_BAD_ARG;
   *out = nullptr;
-  if (original_steps && (!witness_trace || !computational_trace || !permuted_indices || !coefficients || !flag0 ||
-                         !flag1 || !flag2))
-    return STARK_ERR_BAD_ARG;
-  if ((n_public && !public_wires) || (n_public_first && !public_first_indices)) return STARK_ERR_BAD_ARG;
-  STARK_HIP(ctx, hipSetDevice(ctx->device));
-  auto h = std::make_unique<stark_dprove>();
-  hipStream_t s = pick_stream(ctx, stream);
-  const stark_status st = dprove_begin(ctx, world, rank, witness_trace, computational_trace, original_steps,
-                                       public_wires, n_public, public_first_indices, n_public_first, permuted_indices,
-                                       coefficients, flag0, flag1, flag2, nullptr, n_constraints, n_wires, s, h.get());
-  if (st != STARK_OK) {
-    hipStreamSynchronize(s);
-    return st;
-  }
-  *out = h.release();
-  return STARK_OK;
+  const TraceView v{{coefficients, flag0, flag1, flag2, witness_trace, computational_trace}, nullptr,
+                    permuted_indices, original_steps, public_wires, n_public, public_first_indices, n_public_first,
+                    n_constraints, n_wires, false};
+  if (host_trace_null(v)) return STARK_ERR_BAD_ARG;
+  return dprove_open(ctx, world, rank, v, nullptr, stream, out);
 }
-
-}  // extern "C"
-
-stark_status stark::dprove_begin_prepared(stark_ctx* ctx, uint32_t world, uint32_t rank, const uint64_t* witness_trace,
-                                          const uint64_t* computational_trace, size_t os, const uint64_t* public_wires,
-                                          size_t n_public, const size_t* public_first_indices, size_t n_pfi,
-                                          const size_t* permuted_indices, const uint64_t* coefficients,
-                                          const uint8_t* flag_bytes, size_t n_constraints, size_t n_wires,
-                                          const fe* pre, void* stream, stark_dprove** out) {
-  if (!ctx || !out || !pre) return STARK_ERR_BAD_ARG;
-  *out = nullptr;
-  STARK_HIP(ctx, hipSetDevice(ctx->device));
-  auto h = std::make_unique<stark_dprove>();
-  hipStream_t s = pick_stream(ctx, stream);
-  const stark_status st = dprove_begin(ctx, world, rank, witness_trace, computational_trace, os, public_wires,
-                                       n_public, public_first_indices, n_pfi, permuted_indices, coefficients, nullptr,
-                                       nullptr, nullptr, flag_bytes, n_constraints, n_wires, s, h.get(), pre);
-  if (st != STARK_OK) {
-    hipStreamSynchronize(s);
-    return st;
-  }
-  *out = h.release();
-  return STARK_OK;
-}
-
-extern "C" {
 
 stark_status stark_dprove_begin_bytes(stark_ctx* ctx, uint32_t world, uint32_t rank, const uint8_t* r1cs,
                                       size_t r1cs_len, const uint8_t* wtns, size_t wtns_len, void* stream,
@@ -2185,24 +2073,20 @@ stark_status stark_dprove_begin_bytes(stark_ctx* ctx, uint32_t world, uint32_t r
   DevTrace dt;
   stark_status st = r1cs_trace_device(ctx, r1cs, r1cs_len, wtns, wtns_len, &dt);
   if (st != STARK_OK) return st;
-  return dprove_begin_trace(ctx, world, rank, dt, stream, out);
+  STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the trace builder runs on the context stream
+  return dprove_open(ctx, world, rank, dt.view(false), nullptr, stream, out);
 }
 
 }  // extern "C"
 
-stark_status stark::dprove_begin_trace(stark_ctx* ctx, uint32_t world, uint32_t rank, const DevTrace& dt, void* stream,
-                                       stark_dprove** out) {
+stark_status stark::dprove_open(stark_ctx* ctx, uint32_t world, uint32_t rank, const TraceView& v, const fe* pre,
+                                void* stream, stark_dprove** out) {
   if (!ctx || !out) return STARK_ERR_BAD_ARG;
   *out = nullptr;
   STARK_HIP(ctx, hipSetDevice(ctx->device));
-  STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the trace builder runs on the context stream
   auto h = std::make_unique<stark_dprove>();
   hipStream_t s = pick_stream(ctx, stream);
-  const stark_status st = dprove_begin(ctx, world, rank, (const uint64_t*)dt.wit, (const uint64_t*)dt.comp, dt.os,
-                                       dt.public_wires.data(), dt.public_wires.size() / 4,
-                                       dt.public_first_indices.data(), dt.public_first_indices.size() / 2,
-                                       (const size_t*)dt.perm, (const uint64_t*)dt.coef, nullptr, nullptr, nullptr,
-                                       dt.flags, dt.n_constraints, dt.n_wires, s, h.get());
+  const stark_status st = dprove_begin(ctx, world, rank, v, pre, s, h.get());
   if (st != STARK_OK) {
     hipStreamSynchronize(s);
     return st;
@@ -2217,20 +2101,15 @@ stark_status stark_dprove_info(stark_dprove* h, size_t* precision, size_t* n_loc
                                uint64_t g2[4], uint8_t a_root[32]) {
   if (!h) return STARK_ERR_BAD_ARG;
   DProveState& d = h->st;
-  if (precision) *precision = d.prec;
-  if (n_local) *n_local = d.P;
-  if (original_steps) *original_steps = d.os;
+  if (precision) *precision = d.dim.prec;
+  if (n_local) *n_local = d.dim.P;
+  if (original_steps) *original_steps = d.dim.os;
   if (g2) memcpy(g2, d.g2c, 32);
   Transcript t;
   STARK_HIP(d.ctx, hipMemcpyAsync(&t, d.d_tr, sizeof(Transcript), hipMemcpyDeviceToHost, d.s));
   STARK_HIP(d.ctx, hipStreamSynchronize(d.s));
   if (a_root) memcpy(a_root, t.roots[0], 32);
-  if (t.err) {
-    d.ctx->last_error = (t.err & 1) ? "invalid D: Q does not vanish where Z does (utils.rs:379-418)"
-                                    : "invalid B: boundary value mismatch (utils.rs:477-524)";
-    return STARK_ERR_CHECK;
-  }
-  return STARK_OK;
+  return transcript_status(d.ctx, t.err);
 }
 
 stark_status stark_dprove_rows(stark_dprove* h, uint8_t** rows_dev) {
@@ -2250,20 +2129,18 @@ static stark_status dprove_lincomb(stark_dprove* h, const uint8_t* m_root, const
     STARK_HIP(d.ctx, hipMemcpyAsync(d.d_tr->roots[1], m_root, 32, hipMemcpyHostToDevice, d.s));
     d_root = d.d_tr->roots[1];
   }
-  XsPowers xs;
-  for (int t = 0; t < 8; ++t) xs.v[t] = d.xs_m[t];
-  hipLaunchKernelGGL(r1cs_k_kernel, dim3(1), dim3(kKThreads), 0, d.s, (const uint32_t*)d_root, mc.r2, mc.one, xs,
+  hipLaunchKernelGGL(r1cs_k_kernel, dim3(1), dim3(kKThreads), 0, d.s, (const uint32_t*)d_root, mc.r2, mc.one, d.xs,
                      pow32(), d.d_tr);
   STARK_HIP(d.ctx, hipGetLastError());
   LincombArgs la;
   la.rows = d.rows;
   la.plane = 0;
   la.out = d.lvals;
-  la.prec = d.P;
-  la.g_add = d.r;
-  la.log_g = d.log_g;
+  la.prec = d.dim.P;
+  la.g_add = d.dim.rank;
+  la.log_g = d.dim.log_g;
   la.tr = d.d_tr;
-  hipLaunchKernelGGL(r1cs_lincomb_kernel, dim3(blocks_for(d.P)), dim3(256), 0, d.s, la);
+  hipLaunchKernelGGL(r1cs_lincomb_kernel, dim3(blocks_for(d.dim.P)), dim3(256), 0, d.s, la);
   STARK_HIP(d.ctx, hipGetLastError());
   if (m_root) STARK_HIP(d.ctx, hipStreamSynchronize(d.s));  // m_root is the caller's (pageable) buffer
   *l_dev = (uint64_t*)d.lvals;

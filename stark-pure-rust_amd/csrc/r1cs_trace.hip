@@ -118,16 +118,13 @@ struct stark_r1cs_trace {
   U64Array permuted_indices;
   std::vector<uint64_t> public_wires;
   std::vector<size_t> public_first_indices;  // (k, w) pairs
+  stark::TraceView view() const {
+    return {{coefficients.data(), nullptr, nullptr, nullptr, witness_trace.data(), computational_trace.data()},
+            flags.data(), (const size_t*)permuted_indices.data(), coefficients.size() / 4, public_wires.data(),
+            public_wires.size() / 4, public_first_indices.data(), public_first_indices.size() / 2, n_constraints,
+            n_wires, false};
+  }
 };
-
-namespace stark {
-stark_status mk_r1cs_proof_bytes_flags(stark_ctx* ctx, const uint64_t* witness_trace,
-                                      const uint64_t* computational_trace, size_t os, const uint64_t* public_wires,
-                                      size_t n_public, const size_t* public_first_indices, size_t n_pfi,
-                                      const size_t* permuted_indices, const uint64_t* coefficients,
-                                      const uint8_t* flag_bytes, size_t n_constraints, size_t n_wires,
-                                      stark_r1cs_proof** out, bool dev_in);
-}
 
 namespace stark {
 namespace {
@@ -475,11 +472,7 @@ void stark_r1cs_trace_free(stark_r1cs_trace* t) { delete t; }
 
 stark_status stark_prove_r1cs_trace(stark_ctx* ctx, const stark_r1cs_trace* t, stark_r1cs_proof** out) {
   if (!t) return STARK_ERR_BAD_ARG;
-  return mk_r1cs_proof_bytes_flags(ctx, t->witness_trace.data(), t->computational_trace.data(),
-                                   t->coefficients.size() / 4, t->public_wires.data(), t->public_wires.size() / 4,
-                                   t->public_first_indices.data(), t->public_first_indices.size() / 2,
-                                   (const size_t*)t->permuted_indices.data(), t->coefficients.data(),
-                                   t->flags.data(), t->n_constraints, t->n_wires, out);
+  return mk_r1cs_proof_view(ctx, t->view(), nullptr, out);
 }
 
 }  // extern "C"

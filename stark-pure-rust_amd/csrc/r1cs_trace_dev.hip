@@ -871,11 +871,7 @@ stark_status stark_prove_r1cs_bytes(stark_ctx* ctx, const uint8_t* r1cs, size_t 
   if (st != STARK_OK) return st;
   // (a deferred wire-id flag is read with the prover's first download and reported as STARK_ERR_BAD_ARG)
   ctx->trace_err = dt.d_err;
-  st = mk_r1cs_proof_bytes_flags(ctx, (const uint64_t*)dt.wit, (const uint64_t*)dt.comp, dt.os,
-                                 dt.public_wires.data(), dt.public_wires.size() / 4,
-                                 dt.public_first_indices.data(), dt.public_first_indices.size() / 2,
-                                 (const size_t*)dt.perm, (const uint64_t*)dt.coef, dt.flags, dt.n_constraints,
-                                 dt.n_wires, out, true);  // (device columns: one pack launch)
+  st = mk_r1cs_proof_view(ctx, dt.view(true), nullptr, out);  // (device columns: one pack launch)
   ctx->trace_err = nullptr;
   return st;
 }
@@ -905,9 +901,8 @@ stark_status stark_prove_r1cs_circuit(stark_ctx* ctx, const stark_r1cs_circuit* 
   DevTrace dt;
   const stark_status st = circuit_witness(ctx, c, wtns, wtns_len, &dt);
   if (st != STARK_OK) return st;
-  return mk_r1cs_proof_prepared(ctx, (const uint64_t*)dt.wit, (const uint64_t*)dt.comp, c.os, dt.public_wires.data(),
-                                dt.public_wires.size() / 4, c.pfi.data(), c.pfi.size() / 2, (const size_t*)c.perm,
-                                (const uint64_t*)c.coef, c.flags, c.n_c, c.n_wires, (const fe*)c.lde.ptr, out);
+  if (!c.lde.ptr) return STARK_ERR_BAD_ARG;
+  return mk_r1cs_proof_view(ctx, c.view(dt), (const fe*)c.lde.ptr, out);
 }
 
 stark_status stark_dprove_circuit_new(stark_ctx* ctx, uint32_t world, uint32_t rank, const uint8_t* r1cs,
@@ -937,10 +932,8 @@ stark_status stark_dprove_begin_circuit(stark_ctx* ctx, const stark_r1cs_circuit
   stark_status st = circuit_witness(ctx, c, wtns, wtns_len, &dt);
   if (st != STARK_OK) return st;
   STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the witness columns are built on the context stream
-  return dprove_begin_prepared(ctx, c.world, c.rank, (const uint64_t*)dt.wit, (const uint64_t*)dt.comp, c.os,
-                               dt.public_wires.data(), dt.public_wires.size() / 4, c.pfi.data(), c.pfi.size() / 2,
-                               (const size_t*)c.perm, (const uint64_t*)c.coef, c.flags, c.n_c, c.n_wires,
-                               (const fe*)c.lde.ptr, stream, out);
+  if (!c.lde.ptr) return STARK_ERR_BAD_ARG;
+  return dprove_open(ctx, c.world, c.rank, c.view(dt), (const fe*)c.lde.ptr, stream, out);
 }
 
 }  // extern "C"

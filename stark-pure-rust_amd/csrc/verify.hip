@@ -784,13 +784,10 @@ static stark_status verify_r1cs(stark_ctx* ctx, const PreparedCircuit& c, const 
   // parallel pass inside verify_fri; the outcomes are reported in the reference's order.
   std::vector<size_t> positions, aug;
   const bool sampled = sampler(pr.l_root, prec, 80, (uint32_t)skips, positions);
-  if (sampled)
-    for (size_t j : positions) {
-      aug.push_back(j);
-      aug.push_back((j + prec - skips) % prec);
-      aug.push_back((j + os / 3 * skips) % prec);
-      aug.push_back((j + os / 3 * 2 * skips) % prec);
-    }
+  if (sampled) {
+    aug.resize(4 * positions.size());
+    for (size_t i = 0; i < positions.size(); ++i) spot_rows(positions[i], os, skips, prec, &aug[4 * i]);
+  }
   // (zip: every index needs its opening)
   const bool sized = sampled && pr.main.size() >= aug.size() && pr.lcomb.size() >= positions.size();
   std::vector<PathCheck> checks;

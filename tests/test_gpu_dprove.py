@@ -179,3 +179,135 @@ def test_prove_distributed_synth_2_20_vs_oracle_digest(world, prepared):
         finally:
             c.close()
         pytest.fail(f"digest {got} != {want['json_sha256']}: {detail}")
+
+
+# ---- the host-array entry points (stark_dprove_begin, stark_dprove_lincomb), in one process ----------
+#
+# stark_dprove_begin takes the prove.rs-level trace as host arrays with the flags as field elements (seven
+# extended columns, no shared F0); stark_dprove_lincomb takes the main root as host bytes.  The reference
+# for both is the path every other test here pins to the golden digests: stark_dprove_begin_bytes (the
+# device trace builder, flag bytes) and stark_dprove_lincomb_dev, on the same context.
+
+_TRACES = {}
+
+
+def _python_trace(name):
+    """The Python-built trace of a fixture as the arrays stark_dprove_begin takes (built once per name)."""
+    if name not in _TRACES:
+        import numpy as np
+        import r1cs as R
+        from oracle import to_limbs
+        from stark_amd import _elems
+        tr = R.build_trace(*R.load_fixture(FIX, name))
+        u64 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.uint64).reshape(-1))
+        _TRACES[name] = dict(
+            wit=_elems(to_limbs(tr.witness_trace)), comp=_elems(to_limbs(tr.computational_trace)),
+            pub=_elems(to_limbs(tr.public_wires)), coef=_elems(to_limbs(tr.coefficients)),
+            f0=_elems(to_limbs(tr.flag0)), f1=_elems(to_limbs(tr.flag1)), f2=_elems(to_limbs(tr.flag2)),
+            pfi=u64([x for pair in tr.public_first_indices for x in pair]), n_pfi=len(tr.public_first_indices),
+            perm=u64(tr.permuted_indices), n_constraints=tr.n_constraints, n_wires=tr.n_wires)
+    return _TRACES[name]
+
+
+def _begin_pair(ctx, name, world, rank):
+    """(handle of stark_dprove_begin on the Python trace, handle of stark_dprove_begin_bytes on the fixture's
+    bytes) for one rank, both on the context's own stream.  The caller frees them (_free)."""
+    import ctypes
+    from stark_amd import _p64, _szp, _vp
+    t = _python_trace(name)
+    szp = lambda a: a.ctypes.data_as(_szp)
+    ha, hb = _vp(), _vp()
+    try:
+        ctx.check(ctx.lib.stark_dprove_begin(ctx.h, world, rank, _p64(t["wit"]), _p64(t["comp"]), len(t["coef"]),
+                                             _p64(t["pub"]), len(t["pub"]), szp(t["pfi"]), t["n_pfi"],
+                                             szp(t["perm"]), _p64(t["coef"]), _p64(t["f0"]), _p64(t["f1"]),
+                                             _p64(t["f2"]), t["n_constraints"], t["n_wires"], None,
+                                             ctypes.byref(ha)), "dprove_begin")
+        r1 = open(os.path.join(FIX, f"{name}.r1cs"), "rb").read()
+        wt = open(os.path.join(FIX, f"{name}.wtns"), "rb").read()
+        ctx.check(ctx.lib.stark_dprove_begin_bytes(ctx.h, world, rank, r1, len(r1), wt, len(wt), None,
+                                                   ctypes.byref(hb)), "dprove_begin_bytes")
+    except Exception:
+        _free(ctx, ha, hb)
+        raise
+    return ha, hb
+
+
+def _free(ctx, *handles):
+    for h in handles:
+        if h:
+            ctx.lib.stark_dprove_free(h)
+
+
+def _info(ctx, h):
+    """(precision, n_local, original_steps, g2 limbs, a_root) of stark_dprove_info."""
+    import ctypes
+    import numpy as np
+    from stark_amd import _p64
+    v = [ctypes.c_size_t(0) for _ in range(3)]
+    g2 = np.zeros(4, dtype=np.uint64)
+    a_root = ctypes.create_string_buffer(32)
+    ctx.check(ctx.lib.stark_dprove_info(h, *[ctypes.byref(x) for x in v], _p64(g2), a_root), "dprove_info")
+    return v[0].value, v[1].value, v[2].value, tuple(int(x) for x in g2), a_root.raw
+
+
+def _device_bytes(ctx, ptr, nbytes):
+    import numpy as np
+    out = np.empty(nbytes, dtype=np.uint8)
+    ctx.d2h(out, ptr)   # stark_memcpy_d2h, as GpuProverOps.to_host
+    return out
+
+
+def _rows_ptr(ctx, h):
+    import ctypes
+    from stark_amd import _vp
+    p = _vp()
+    ctx.check(ctx.lib.stark_dprove_rows(h, ctypes.byref(p)), "dprove_rows")
+    return p.value
+
+
+@pytest.mark.parametrize("name,world,rank", [("compute", 2, 0), ("compute", 2, 1), ("compute", 8, 5),
+                                             ("poseidon3_test", 4, 3)])
+def test_dprove_begin_host_arrays_equals_bytes(ctx, name, world, rank):
+    """stark_dprove_begin on the Python-built trace gives the rank state of stark_dprove_begin_bytes: the
+    same sizes, g2 and a_root, and the same n_local x 256 bytes of constraint rows.  (compute at world 8:
+    P = steps = 16, the edge of degree < steps <= P; poseidon3_test: 6684 steps padded to 8192.)"""
+    import numpy as np
+    ha, hb = _begin_pair(ctx, name, world, rank)
+    try:
+        ia, ib = _info(ctx, ha), _info(ctx, hb)
+        assert ia == ib
+        prec, n_local, os_ = ia[:3]
+        assert n_local == prec // world and os_ == len(_python_trace(name)["coef"])
+        ra = _device_bytes(ctx, _rows_ptr(ctx, ha), n_local * 256)
+        rb = _device_bytes(ctx, _rows_ptr(ctx, hb), n_local * 256)
+        assert np.array_equal(ra, rb)
+    finally:
+        _free(ctx, ha, hb)
+
+
+def test_dprove_lincomb_host_root_equals_device_root(ctx):
+    """stark_dprove_lincomb (the main root as host bytes) gives the L of stark_dprove_lincomb_dev (the same
+    32 bytes in device memory), on the handle pair of compute at (2, 0) with the golden m_root."""
+    import ctypes
+    import numpy as np
+    from stark_amd import _vp
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "r1cs_proofs.json")))
+    m_root = bytes.fromhex(golden["compute"]["m_root"])
+    assert len(m_root) == 32
+    ha, hb = _begin_pair(ctx, "compute", 2, 0)
+    d_root = ctx.alloc(32)
+    try:
+        n_local = _info(ctx, ha)[1]
+        assert _info(ctx, hb)[1] == n_local
+        la, lb = _vp(), _vp()
+        ctx.check(ctx.lib.stark_dprove_lincomb(ha, m_root, ctypes.byref(la)), "dprove_lincomb")
+        ctx.h2d(d_root, np.frombuffer(m_root, dtype=np.uint8))
+        ctx.check(ctx.lib.stark_dprove_lincomb_dev(hb, d_root, ctypes.byref(lb)), "dprove_lincomb_dev")
+        ctx.synchronize()
+        a = _device_bytes(ctx, la.value, n_local * 32)
+        b = _device_bytes(ctx, lb.value, n_local * 32)
+        assert a.any() and np.array_equal(a, b)
+    finally:
+        ctx.free(d_root)
+        _free(ctx, ha, hb)

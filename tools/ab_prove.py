@@ -59,9 +59,9 @@ def main():
         for lib in a.libs:
             r = subprocess.run([sys.executable, "-c", CHILD, lib, ROOT, a.fixtures, str(a.reps)], capture_output=True,
                                text=True, timeout=300)
-            if r.returncode != 0:
+            if r.returncode != 0:  # (a child that died on the GPU is not followed by more GPU programs)
                 print(f"{lib}: rc {r.returncode} {r.stderr[-500:]}", flush=True)
-                continue
+                sys.exit(1)
             for name, v in json.loads(r.stdout.strip().splitlines()[-1]).items():
                 e = res[lib].setdefault(name, {"ms": [], "digest": v["digest"]})
                 e["ms"] += v["ms"]
