@@ -322,6 +322,8 @@ void stark_ctx_destroy(stark_ctx* ctx) {
     if (kv.second->d_lo) hipFree(kv.second->d_lo);
     if (kv.second->d_full) hipFree(kv.second->d_full);
     if (kv.second->d_full_s) hipFree(kv.second->d_full_s);
+    for (uint32_t* r : kv.second->d_res)
+      if (r) hipFree(r);
     for (hipEvent_t e : kv.second->full_ev)
       if (e) hipEventDestroy(e);
   }

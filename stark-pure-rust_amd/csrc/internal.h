@@ -83,6 +83,11 @@ struct Twiddles {
   // the two of lo * hi, for one 32-B coalesced read.
   fe* d_full = nullptr;
   fe* d_full_s = nullptr;
+  // What each slot holds ([1]: d_full_s): the last pass's log2 radix for the table above, or kFullFused for
+  // the fused producer's per-element table (ntt.hip fused_tw_kernel), which takes its place in a plan whose
+  // last boundary is fused-streamed.  A call that needs the other kind rebuilds the slot.
+  static constexpr uint32_t kFullFused = 0x100;
+  uint32_t full_kind[2] = {0, 0};
   uint64_t full_used = 0, full_s_used = 0;  // cache clock of their last use (LRU eviction, cache_reserve)
   // The fill of d_full / d_full_s ([1]) is enqueued on the stream of the call that first needs it;
   // a call on another stream waits for this event until the fill is known to be complete (fill = null).
@@ -94,6 +99,9 @@ struct Twiddles {
   // radix-4 steps (ntt.hip DbPlan).  db_off[l] = offset in u32 into d_db (72 u32 per root).
   uint32_t* d_db = nullptr;
   uint32_t db_off[16] = {0};
+  // Residual digit-basis tables of the fused passes (ntt.hip): d_res[m] holds w_{2^m}^e, e < 2^m (72 u32
+  // each), m = 4 + log2 of the consumer's radix; built for the boundaries a size's plan fuses.
+  uint32_t* d_res[13] = {nullptr};
   HostFp root;      // the root these tables were built for (Montgomery)
   HostFp inv_n;     // n^-1 (Montgomery)
 };

@@ -30,6 +30,11 @@ struct ColTw {
   const fe* full;   // last pass only: full[c R + r] = w^(c r) (or null)
   uint32_t l16, kb;
   const fe* post;   // last pass only: output k is multiplied by post[k] (Montgomery), or null
+  // Fused producer passes only (kFuseStaged / kFuseStreamed below):
+  const uint32_t* res;  // residual digit-basis table: w_{16 R'}^e, e < 16 R' (72 u32 each)
+  const fe* fused;      // streamed: the tile-ordered merged twiddles (fused_tw_kernel), Montgomery
+  uint32_t log_rp;      // log2 of the next pass's radix R'
+  uint32_t log_q;       // r' = column >> log_q, log_q = log2(n / (R R')) >= log_b
 };
 
 // One Stockham pass (see the file comment): each workgroup transforms one tile of B adjacent
@@ -110,6 +115,20 @@ __device__ __forceinline__ const uint32_t* dbt(const uint32_t* sdb, uint32_t k) 
 enum : int { kColNone = 0, kColFull = 1, kColT16 = 2, kColTwoLevel = 3, kColSparse = 4 };
 // (kColSparse: a first pass over a zero-padded input (Sparse::skip > 0); no column twiddle either.)
 
+// FUSE: a radix-2^8 16 x 16 pass that also applies the NEXT pass's column twiddle, so that pass runs as
+// kColNone.  The next pass (radix R', N' = Ns R R') reads this pass's output row k of column j
+// (c = j mod Ns) as its row r' = j div (n / (R R')), one value per tile, and would multiply it by
+// w_N'^((c + Ns k) r').  With k = k1 + 16 k2 that is
+//   w_N'^((c + Ns k1) r'), merged into the pass's own twiddle w_R^(r1 k1) (one per-lane product, as before),
+//   w_{16 R'}^(k2 r'), wave-uniform in the last radix-4 step (k2 = (q >> 4) + 4 kk): a digit-basis product
+//     of the four outputs by a constant in SGPRs, from the residual table ColTw::res.
+// kFuseStaged: the transform's dense first pass (Ns = 1, c = 0, N' <= 2^l16): the tile stages its 256 merged
+//   Shoup pairs from the t16 table (slot 16 g + t: index ((N'/R) r1 k1 + k1 r') mod N', r1 = rev4(g), k1 = t).
+// kFuseStreamed: N' = n: the merged twiddles stream from a per-element table laid out in the order the
+//   twiddle step reads it ([tile][kk][tid], Montgomery; ColTw::fused), which takes the full table's place.
+// Both need a full 1024-element tile (one a per wave) and log_q >= log_b (one r' per tile).
+enum : int { kFuseNone = 0, kFuseStaged = 1, kFuseStreamed = 2 };
+
 // Elements per workgroup tile: 2^10 (B = 1024 / R columns, 256 threads).  4096- and 2048-element
 // tiles measured slower (one or two workgroups per CU leave the barriers uncovered).
 constexpr uint32_t kTileLog = 10;
@@ -187,7 +206,7 @@ struct XImage {
   }
 };
 
-template <int LOG_R, int COL>
+template <int LOG_R, int COL, int FUSE = kFuseNone>
 __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void ntt_pass_kernel(
     const fe* __restrict__ in, fe* __restrict__ out, uint32_t log_n, uint32_t log_ns, uint32_t log_b, ColTw ct,
     const fe* __restrict__ small, const uint32_t* __restrict__ db, fe scale, int do_scale, uint32_t log_tiles,
@@ -198,6 +217,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
   // 2^26 (6, 6, 6, 8); in the 16 x 16 radix-2^8 passes it was 1.1 % slower at 2^24, and 2 % slower in the
   // radix-2^4 pass of 2^20 (profiles/r05_csub_top_ab.txt).
   constexpr bool FAST = LOG_R == 6;
+  static_assert(FUSE == kFuseNone || (LOG_R == 8 && (COL == kColNone || (COL == kColT16 && FUSE == kFuseStreamed))),
+                "fused producers are the dense radix-2^8 passes");
   extern __shared__ __attribute__((aligned(16))) fe lds[];
   fe* sm = lds;          // R/2 small roots w_R^k as Shoup pairs: sm[2k] = w_R^k, sm[2k + 1] = its quotient
   uint32_t* sdb = reinterpret_cast<uint32_t*>(lds + DB::shoup_fe);  // digit-basis tables (DbPlan)
@@ -212,6 +233,7 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
   const uint32_t tile_mask = (1u << log_tiles) - 1;
   const uint32_t tile = blockIdx.x;
   if (tile >= total_tiles) return;  // (uniform per workgroup)
+  const uint32_t rp = FUSE ? ((tile & tile_mask) << log_b) >> ct.log_q : 0;  // the next pass's row r' of this tile
 
   // This thread's 4 elements of a tile: (eb[t], er[t]) = (column, row) as stored and loaded.
   uint32_t eb[4], er[4];
@@ -241,13 +263,24 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
   // store, so a wave waits for one memory latency instead of one per staging round.  (The global
   // digit-basis table holds every w_R^k, k < R/2; the LDS copy every stride-th one.)
   {
-    constexpr uint32_t kSm = 2 * DB::shoup_fe, kDb = DB::on ? DB::entries * 18 : 0;  // 16-B units
+    // (a streamed producer's twiddles come from its table: nothing staged; a staged one gathers from t16)
+    constexpr uint32_t kSm = FUSE == kFuseStreamed ? 0 : 2 * DB::shoup_fe, kDb = DB::on ? DB::entries * 18 : 0;  // 16-B units
     const uint4* db4 = reinterpret_cast<const uint4*>(db);
     const uint4* small4 = reinterpret_cast<const uint4*>(small);
     uint4* sm4 = reinterpret_cast<uint4*>(sm);
     uint4* sdb4 = reinterpret_cast<uint4*>(sdb);
     auto db_src = [&](uint32_t k) { const uint32_t e = k / 18; return (e * DB::stride) * 18 + (k - e * 18); };
     auto db_dst = [&](uint32_t k) { return k + ((k / 18) >> 3); };
+    auto sm_src = [&](uint32_t u) -> const uint4* {
+      if (FUSE == kFuseStaged) {
+        const uint32_t slot = u >> 2, t = slot & (R / 16 - 1);
+        const uint32_t r1 = __builtin_bitreverse32(slot / (R / 16)) >> 28;
+        const uint32_t lnp = LOG_R + ct.log_rp;
+        const uint32_t idx = (((r1 * t) << ct.log_rp) + t * rp) & ((1u << lnp) - 1);
+        return reinterpret_cast<const uint4*>(ct.t16) + ((((size_t)idx << (ct.l16 - lnp)) << 2) + (u & 3));
+      }
+      return small4 + u;
+    };
     if (blockDim.x == kPassThreads) {
       constexpr uint32_t nSm = (kSm + kPassThreads - 1) / kPassThreads, nDb = (kDb + kPassThreads - 1) / kPassThreads;
       // (full rounds need no bounds test: tid < kPassThreads here)
@@ -256,7 +289,7 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       uint4 ts[nSm ? nSm : 1], td[nDb ? nDb : 1];
 #pragma unroll
       for (uint32_t i = 0; i < nSm; ++i)
-        if (in_sm(i)) ts[i] = small4[tid + i * kPassThreads];
+        if (in_sm(i)) ts[i] = *sm_src(tid + i * kPassThreads);
 #pragma unroll
       for (uint32_t i = 0; i < nDb; ++i)
         if (in_db(i)) td[i] = db4[db_src(tid + i * kPassThreads)];
@@ -267,7 +300,7 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       for (uint32_t i = 0; i < nDb; ++i)
         if (in_db(i)) sdb4[db_dst(tid + i * kPassThreads)] = td[i];
     } else {
-      for (uint32_t k = tid; k < kSm; k += blockDim.x) sm4[k] = small4[k];
+      for (uint32_t k = tid; k < kSm; k += blockDim.x) sm4[k] = *sm_src(k);
       for (uint32_t k = tid; k < kDb; k += blockDim.x) sdb4[db_dst(k)] = db4[db_src(k)];
     }
   }
@@ -346,6 +379,18 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       }
     }
   }
+  // A streamed producer's four merged twiddles ([tile][kk][tid]: 8 KB contiguous per kk), issued after
+  // the jj-major step's barrier, where that step's registers are free (165 VGPRs).  Issued before it
+  // (STARK_FUSED_TW_EARLY, so that they fly during the step) the pass spills 38 VGPRs.
+  fe ftw[4];
+  auto load_ftw = [&]() {
+    const fe* f = ct.fused + ((size_t)(tile & tile_mask) << (LOG_R + log_b)) + tid;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ftw[k] = fe_load_nt(f + (uint32_t)k * nthr);
+  };
+#ifdef STARK_FUSED_TW_EARLY
+  if (FUSE == kFuseStreamed && active) load_ftw();
+#endif
   __syncthreads();
 
   // ---- R-point DIT over the bit-reversed image ----
@@ -431,6 +476,9 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       XI.st(i0 + 3 * st, x3);
     }
     __syncthreads();
+#ifndef STARK_FUSED_TW_EARLY
+    if (FUSE == kFuseStreamed && active) load_ftw();
+#endif
     s = kS0 + 2;
   }
   // ---- radix 2^8 / 2^7 as T x 16 (DbPlan::four): twiddles, then a 16-point DFT across the groups ----
@@ -448,10 +496,22 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       const uint32_t i0 = (((a << (LT + 2)) + t) << log_b) + b, st = (1u << LT) << log_b;
       fe x[4];
       // (group g = 0's twiddle is w^0: with one a per wave the a = 0 waves skip that product)
-      const bool unit0 = ((64u >> log_b) <= (1u << LT) ? __builtin_amdgcn_readfirstlane(a) : a) == 0;
+      // (a fused pass's merged twiddle of group 0 is not 1)
+      const bool unit0 = FUSE == kFuseNone && ((64u >> log_b) <= (1u << LT) ? __builtin_amdgcn_readfirstlane(a) : a) == 0;
+      if (FUSE == kFuseStreamed) {
+        const fe v0 = XI.ld(i0), v1 = XI.ld(i0 + st), v2 = XI.ld(i0 + 2 * st), v3 = XI.ld(i0 + 3 * st);
+        mul2(x[0], x[1], v0, ftw[0], v1, ftw[1]);  // [0, 4p) x Montgomery image -> [0, 2p)
+        mul2(x[2], x[3], v2, ftw[2], v3, ftw[3]);
+      }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
+        if (FUSE == kFuseStreamed) break;
         const fe v = XI.ld(i0 + k * st);
+        if (FUSE == kFuseStaged) {
+          const uint32_t slot = (((a << 2) + k) << LT) + t;  // the pair of (g, t)
+          x[k] = fe_mul_shoup(v, sm[2 * slot], sm[2 * slot + 1]);
+          continue;
+        }
         if (k == 0 && unit0) {
           x[0] = v;
           fe_csub2p(x[0]);  // [0, 4p) -> [0, 2p)
@@ -508,6 +568,18 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       yl[1] = x1;
       yl[2] = x2;
       yl[3] = x3;
+      if (FUSE != kFuseNone) {
+        // residual of the next pass's twiddle: output row q + 64 kk has k2 = (q >> 4) + 4 kk, one per wave
+        const uint32_t k2 = __builtin_amdgcn_readfirstlane(q >> LT);
+#pragma unroll
+        for (uint32_t kk = 0; kk < 4; ++kk) {
+          const uint32_t e = (k2 + 4 * kk) * rp;  // < 16 R'
+          if (e == 0)
+            fe_csub2p(yl[kk]);  // [0, 4p) -> [0, 2p), what the next pass's first stage takes
+          else
+            yl[kk] = fe_mul_db(yl[kk], ct.res + 72u * e);
+        }
+      }
     }
     kept = true;
     s = LOG_R;
@@ -812,7 +884,14 @@ pass_fn pass_kernel_r(int col) {
   }
 }
 
-pass_fn pass_kernel(uint32_t log_r, int col) {
+pass_fn pass_kernel(uint32_t log_r, int col, int fuse = kFuseNone) {
+  if (fuse != kFuseNone) {  // radix 2^8, dense (ntt_device_plan selects nothing else)
+    if (log_r != 8) return nullptr;
+    if (fuse == kFuseStaged) return col == kColNone ? ntt_pass_kernel<8, kColNone, kFuseStaged> : nullptr;
+    return col == kColNone  ? ntt_pass_kernel<8, kColNone, kFuseStreamed>
+           : col == kColT16 ? ntt_pass_kernel<8, kColT16, kFuseStreamed>
+                            : nullptr;
+  }
   switch (log_r) {
     case 2: return pass_kernel_r<2>(col);
     case 3: return pass_kernel_r<3>(col);
@@ -826,7 +905,59 @@ pass_fn pass_kernel(uint32_t log_r, int col) {
   }
 }
 
+// Fusion policy of a transform (ntt_pass_kernel FUSE): the size's own choice, or a test's.
+enum : int { kFuseAuto = 0, kFuseAll = 1, kFuseForceStreamed = 2, kFuseOff = 3 };
+
+// Modes a size's own plan may use (bit kFuseStaged / kFuseStreamed): those whose boundary, enabled on its
+// own, beat the unfused build by more than three times that build's round-to-round spread in two
+// same-process A/B runs.  2^24: the staged boundary 1 -> 2; its streamed boundary 2 -> 3
+// measured -1.2 % on its own (-2.4 % on top of the staged one) and missed that bar in one run of four.
+// 2^20 (staged) and 2^23 (streamed) measured no gain; 2^16 cannot fuse (fuse_modes).
+inline uint32_t fuse_default(uint32_t log_n) {
+#ifdef STARK_FUSE_ALL_SIZES  // timing builds: every boundary that can fuse, at every size
+  return (1u << kFuseStaged) | (1u << kFuseStreamed);
+#endif
+#ifdef STARK_FUSE_ONLY  // timing builds: 2^24 with one mode's boundary (1 staged, 2 streamed), the per-boundary A/B
+  return log_n == 24 ? 1u << STARK_FUSE_ONLY : 0;
+#endif
+  return log_n == 24 ? 1u << kFuseStaged : 0;
+}
+
+// fz[p] = producer mode of pass p for the boundary p -> p + 1 (the last pass: none).  A boundary can
+// fuse when the producer is a dense radix-2^8 pass over full 1024-element tiles, the consumer's radix
+// R' <= 2^8 and its row r' = column >> log_q is one per tile; staged additionally when the producer is
+// the first pass and N' = R R' fits the t16 table, streamed when the consumer is the transform's last
+// pass of radix 2^8 (the table is per (root, n, direction): Ns = n / 2^16) at a cacheable size.
+void fuse_modes(const PassPlan& plan, uint32_t log_n, uint32_t l16, int policy, bool dense_first, int fz[8]) {
+  for (int p = 0; p < 8; ++p) fz[p] = kFuseNone;
+  const uint32_t allowed = policy == kFuseAuto ? fuse_default(log_n) : ~0u;
+  if (policy == kFuseOff || !allowed) return;
+  uint32_t log_ns = 0;
+  for (int p = 0; p + 1 < plan.n_pass; log_ns += plan.log_r[p], ++p) {
+    const uint32_t lr = plan.log_r[p], lrn = plan.log_r[p + 1];
+    if (lr != 8 || lrn > 8 || log_n < lr + lrn) continue;
+    const uint32_t lb = choose_log_b_impl(log_n, lr, kTileLog);
+    if (lb != kTileLog - 8 || log_n - lr - lrn < lb) continue;
+    if (p == 0 && !dense_first) continue;
+    const bool fused_in = p > 0 && fz[p - 1] != kFuseNone;
+    const bool staged = p == 0 && lr + lrn <= l16;
+    // (the producer's own column twiddle: none, or Shoup pairs from t16)
+    const bool streamed = p + 2 == plan.n_pass && lrn == 8 && log_n >= 18 && log_n <= 26 &&
+                          (p == 0 || fused_in || log_ns + lr <= l16);
+    if (policy == kFuseForceStreamed)
+      fz[p] = streamed ? kFuseStreamed : staged ? kFuseStaged : kFuseNone;
+    else
+      fz[p] = staged ? kFuseStaged : streamed ? kFuseStreamed : kFuseNone;
+    if (!(allowed >> fz[p] & 1)) fz[p] = kFuseNone;
+  }
+}
+
 }  // namespace
+
+static stark_status res_table(stark_ctx* ctx, Twiddles& tw, uint32_t m);
+static stark_status ntt_device_plan(stark_ctx* ctx, const fe* src, uint32_t zero_log, fe* d_data, uint32_t log_n,
+                                    uint32_t batch, const Twiddles& tw, bool inverse, hipStream_t stream,
+                                    const fe* post, const PassPlan& plan, int policy, uint32_t* used = nullptr);
 
 stark_status get_twiddles(stark_ctx* ctx, const uint64_t root[4], uint32_t log_n, const Twiddles** out) {
   const FieldHost& F = FieldHost::get();
@@ -951,6 +1082,22 @@ stark_status get_twiddles(stark_ctx* ctx, const uint64_t root[4], uint32_t log_n
   STARK_HIP(ctx, hipMemcpy(tw->d_hi_s, h_hi_s.data(), n_hi * sizeof(fe), hipMemcpyHostToDevice));
   STARK_HIP(ctx, hipMemcpy(tw->d_t16_s, h_t16_s.data(), 2 * n16 * sizeof(fe), hipMemcpyHostToDevice));
   STARK_HIP(ctx, hipMemcpy(tw->d_db, h_db.data(), h_db.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  // Residual tables of the boundaries this size's plan fuses.
+  if (log_n >= 2) {
+    const PassPlan plan = plan_passes(log_n);
+    int fz[8];
+    fuse_modes(plan, log_n, tw->l16, kFuseAuto, true, fz);
+    for (int p = 0; p + 1 < plan.n_pass; ++p)
+      if (fz[p] != kFuseNone) {
+        const stark_status st = res_table(ctx, *tw, 4 + plan.log_r[p + 1]);
+        if (st != STARK_OK) {
+          for (uint32_t* r : tw->d_res)
+            if (r) hipFree(r);
+          hipFree(tw->d_lo);
+          return st;
+        }
+      }
+  }
   *out = tw.get();
   ctx->tw.emplace(key, std::move(tw));
   return STARK_OK;
@@ -967,34 +1114,96 @@ __global__ void full_tw_kernel(const fe* __restrict__ lo, const fe* __restrict__
   fe_store(out + g, t);
 }
 
-// The last pass's full twiddle table, built once per (root, n, direction) and kept in the context's
-// size-capped cache (cache_reserve: least recently used tables go first).  When it cannot be cached
-// (larger than the cap, or no device memory) *out is null and the pass takes the two-level form.
-static stark_status full_table(stark_ctx* ctx, const Twiddles& tw_c, uint32_t log_r, bool scaled, hipStream_t stream,
+// The fused-streamed producer's merged twiddles (ntt_pass_kernel, kFuseStreamed: radix 2^8 before a last
+// pass of radix 2^8, Ns = n / 2^16, 1024-element tiles of B = 4 columns), in the order its twiddle step
+// reads them: out[tile][kk][tid] = w^E, E = (n/R) r1 k1 + (c + Ns k1) r' mod n, for thread tid = 4 q + b's
+// image row 16 g + t (t = k1 = q & 15, g = 4 (q >> 4) + kk, r1 = rev4(g)), column j = 4 tile + b,
+// c = j mod Ns, r' = j div (n / 2^16).  Times `scale` when given.
+__global__ void fused_tw_kernel(const fe* __restrict__ lo, const fe* __restrict__ hi, uint32_t kb, uint32_t log_n,
+                                fe scale, int do_scale, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >> log_n) return;
+  const uint32_t log_ns = log_n - 16;
+  const uint32_t tid = (uint32_t)g & 255, kk = ((uint32_t)g >> 8) & 3;
+  const uint64_t j = ((g >> 10) << 2) + (tid & 3);
+  const uint32_t q = tid >> 2, k1 = q & 15;
+  const uint32_t r1 = __builtin_bitreverse32(((q >> 4) << 2) + kk) >> 28;
+  const uint64_t c = j & (((uint64_t)1 << log_ns) - 1), rp = j >> log_ns;
+  const uint64_t e = (((uint64_t)(r1 * k1) << (log_n - 8)) + (c + ((uint64_t)k1 << log_ns)) * rp) &
+                     (((uint64_t)1 << log_n) - 1);
+  fe t = fe_mul(lo[e & (((uint64_t)1 << kb) - 1)], hi[e >> kb]);
+  if (do_scale) t = fe_mul(t, scale);
+  fe_store(out + g, t);
+}
+
+// The last pass's full twiddle table (kind = that pass's log2 radix), or the table of the fused-streamed
+// producer before it (kind = Twiddles::kFullFused), which takes its place: one slot per (root, n,
+// direction), built on first use and kept in the context's size-capped cache (cache_reserve: least
+// recently used tables go first).  A slot that holds the other kind is rebuilt.  When the table cannot be
+// cached (larger than the cap, or no device memory) *out is null: the last pass takes the two-level form,
+// a fused boundary its unfused one.
+static stark_status full_table(stark_ctx* ctx, const Twiddles& tw_c, uint32_t kind, bool scaled, hipStream_t stream,
                                const fe** out) {
   Twiddles& tw = const_cast<Twiddles&>(tw_c);  // lazily filled cache entry
   fe*& slot = scaled ? tw.d_full_s : tw.d_full;
   const int d = scaled ? 1 : 0;
   (scaled ? tw.full_s_used : tw.full_used) = ++ctx->cache_clock;
+  if (slot && tw.full_kind[d] != kind) {
+    STARK_HIP(ctx, hipDeviceSynchronize());  // (a kernel of any stream may still read it)
+    hipFree(slot);
+    slot = nullptr;
+    tw.full_fill[d] = nullptr;
+  }
   if (!slot) {
     const uint64_t n = (uint64_t)1 << tw.log_n;
     void* p = nullptr;
     if (!cache_reserve(ctx, n * sizeof(fe), false) || hipMalloc(&p, n * sizeof(fe)) != hipSuccess) {
       hipGetLastError();  // (a failed allocation is not an error here)
-      *out = nullptr;     // no room: fall back to the two-level form
+      *out = nullptr;     // no room
       return STARK_OK;
     }
-    hipLaunchKernelGGL(full_tw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tw.d_lo, tw.d_hi,
-                       tw.kb, log_r, n, to_dev(tw.inv_n), scaled ? 1 : 0, (fe*)p);
+    if (kind == Twiddles::kFullFused)
+      hipLaunchKernelGGL(fused_tw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tw.d_lo, tw.d_hi,
+                         tw.kb, tw.log_n, to_dev(tw.inv_n), scaled ? 1 : 0, (fe*)p);
+    else
+      hipLaunchKernelGGL(full_tw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tw.d_lo, tw.d_hi,
+                         tw.kb, kind, n, to_dev(tw.inv_n), scaled ? 1 : 0, (fe*)p);
     STARK_HIP(ctx, hipGetLastError());
     // Published now, complete only when the fill has run on `stream`: a call on another stream
     // waits for this event (fill_wait below) instead of reading a table still being written.
     STARK_TRY(fill_mark(ctx, tw.full_ev[d], tw.full_fill[d], stream));
     slot = (fe*)p;
+    tw.full_kind[d] = kind;
   } else {
     STARK_TRY(fill_wait(ctx, tw.full_ev[d], tw.full_fill[d], stream));
   }
   *out = slot;
+  return STARK_OK;
+}
+
+// Residual digit-basis table of a fused boundary whose consumer has radix 2^(m - 4): w_{2^m}^e, e < 2^m
+// (ntt_pass_kernel FUSE; 1.18 MB for m = 12).  get_twiddles builds those of the size's own plan.
+static stark_status res_table(stark_ctx* ctx, Twiddles& tw, uint32_t m) {
+  if (m > 12 || m > tw.log_n) return STARK_ERR_BAD_ARG;
+  if (tw.d_res[m]) return STARK_OK;
+  const FieldHost& F = FieldHost::get();
+  const size_t cnt = (size_t)1 << m;
+  std::vector<uint32_t> h(72 * cnt);
+  const HostFp wm = F.pow_u64(tw.root, (uint64_t)1 << (tw.log_n - m));
+  HostFp a = F.one();
+  for (size_t e = 0; e < cnt; ++e) {
+    db_table(a, &h[72 * e]);
+    a = F.mul(a, wm);
+  }
+  void* d = nullptr;
+  if (hipMalloc(&d, h.size() * sizeof(uint32_t)) != hipSuccess) return STARK_ERR_OOM;
+  const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    hipFree(d);
+    return hip_fail(ctx, e, "hipMemcpy(residual table)");
+  }
+  tw.d_res[m] = (uint32_t*)d;
+  tw.base_bytes += h.size() * sizeof(uint32_t);
   return STARK_OK;
 }
 
@@ -1005,6 +1214,38 @@ extern "C" uint32_t stark_ntt_plan(uint32_t log_n, uint32_t* log_r, uint32_t cap
   const stark::PassPlan p = stark::plan_passes(log_n);
   for (int i = 0; i < p.n_pass && (uint32_t)i < cap; ++i) log_r[i] = p.log_r[i];
   return (uint32_t)p.n_pass;
+}
+
+// Test hook (not part of the ABI of include/stark_hip.h): stark_ntt_dev by a caller-given pass plan
+// (log2 radices, first pass first, summing to log_n) and fusion policy: 0 the size's default, 1 every
+// boundary that can fuse, 2 the same with the streamed mode preferred where both apply, 3 none.
+// *used (optional) receives the producer mode each pass ran in, two bits per pass (1 staged, 2 streamed).
+extern "C" int stark_test_ntt_plan(stark_ctx* ctx, uint64_t* d_data, uint32_t log_n, uint32_t batch,
+                                   const uint64_t root[4], int inverse, const uint32_t* log_r, uint32_t n_pass,
+                                   int policy, void* stream, uint32_t* used) {
+  using namespace stark;
+  if (!ctx || !d_data || !root || !log_r || n_pass == 0 || n_pass > 8 || log_n < 2 || log_n > 28 || policy < 0 ||
+      policy > 3)
+    return STARK_ERR_BAD_ARG;
+  PassPlan plan;
+  plan.n_pass = (int)n_pass;
+  uint32_t sum = 0;
+  for (uint32_t i = 0; i < n_pass; ++i) {
+    if (log_r[i] < 2 || log_r[i] > kMaxLogR) return STARK_ERR_BAD_ARG;
+    plan.log_r[i] = log_r[i];
+    sum += log_r[i];
+  }
+  if (sum != log_n) return STARK_ERR_BAD_ARG;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const FieldHost& F = FieldHost::get();
+  uint64_t use_root[4];
+  memcpy(use_root, root, 32);
+  if (inverse) F.to_canonical(F.inv(F.from_canonical(root)), use_root);
+  if (used) *used = 0;
+  const Twiddles* tw = nullptr;
+  STARK_TRY(get_twiddles(ctx, use_root, log_n, &tw));
+  return ntt_device_plan(ctx, nullptr, 0, (fe*)d_data, log_n, batch, *tw, inverse != 0, pick_stream(ctx, stream),
+                         nullptr, plan, policy, used);
 }
 
 namespace stark {
@@ -1022,9 +1263,17 @@ stark_status ntt_device(stark_ctx* ctx, fe* d_data, uint32_t log_n, uint32_t bat
 // padded coefficients).
 stark_status ntt_device_from(stark_ctx* ctx, const fe* src, uint32_t zero_log, fe* d_data, uint32_t log_n,
                              uint32_t batch, const Twiddles& tw, bool inverse, hipStream_t stream, const fe* post) {
+  return ntt_device_plan(ctx, src, zero_log, d_data, log_n, batch, tw, inverse, stream, post,
+                         log_n >= 2 ? plan_passes(log_n) : PassPlan(), kFuseAuto);
+}
+
+// The transform by a given pass plan (ntt_device_from: the size's own) and fusion policy.
+static stark_status ntt_device_plan(stark_ctx* ctx, const fe* src, uint32_t zero_log, fe* d_data, uint32_t log_n,
+                                    uint32_t batch, const Twiddles& tw, bool inverse, hipStream_t stream,
+                                    const fe* post, const PassPlan& plan, int policy, uint32_t* used) {
   if (batch == 0) return STARK_OK;
   if (src && zero_log > log_n) return STARK_ERR_BAD_ARG;
-  if (src && (zero_log == 0 || log_n < 2 || zero_log > plan_passes(log_n).log_r[0])) {
+  if (src && (zero_log == 0 || log_n < 2 || zero_log > plan.log_r[0])) {
     // Not expressible as a sparse first pass: materialise the padded columns.
     const uint64_t total = (uint64_t)batch << log_n;
     hipLaunchKernelGGL(pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, d_data,
@@ -1042,7 +1291,21 @@ stark_status ntt_device_from(stark_ctx* ctx, const fe* src, uint32_t zero_log, f
     STARK_HIP(ctx, hipGetLastError());
     return STARK_OK;
   }
-  const PassPlan plan = plan_passes(log_n);
+  // Fused boundaries (fuse_modes): fz[p] is pass p's producer mode.  A streamed producer needs its cached
+  // table; without it the whole transform takes the unfused path.
+  int fz[8];
+  fuse_modes(plan, log_n, tw.l16, policy, src == nullptr, fz);
+  const fe* fused_tab = nullptr;
+  for (int p = 0; p + 1 < plan.n_pass; ++p)
+    if (fz[p] == kFuseStreamed) {
+      STARK_TRY(full_table(ctx, tw, Twiddles::kFullFused, inverse, stream, &fused_tab));
+      if (!fused_tab)
+        for (int& f : fz) f = kFuseNone;
+    }
+  if (used)  // (the test hook: which mode each pass ran in, two bits per pass)
+    for (int p = 0; p + 1 < plan.n_pass; ++p) *used |= (uint32_t)fz[p] << (2 * p);
+  for (int p = 0; p + 1 < plan.n_pass; ++p)
+    if (fz[p] != kFuseNone) STARK_TRY(res_table(ctx, const_cast<Twiddles&>(tw), 4 + plan.log_r[p + 1]));
   // The ping-pong buffer is the context's, shared by every stream that calls in: this stream waits
   // for the last use on another one (buf_acquire) and marks its own after the passes (buf_release).
   // (A single-pass transform never touches it.)
@@ -1077,22 +1340,36 @@ stark_status ntt_device_from(stark_ctx* ctx, const fe* src, uint32_t zero_log, f
     const uint64_t total = (uint64_t)batch << log_tiles;
     // Inverse: n^-1 rides on the last pass's column twiddles (scaled tables)
     // when that pass has them (log_ns > 0), else it is an explicit product.
-    const bool fold = inverse && last && log_ns > 0;
+    // A pass after a fused boundary has no column twiddle (the producer applied it, with the inverse's
+    // n^-1 when this is the last pass).
+    const bool fused_in = p > 0 && fz[p - 1] != kFuseNone;
+    const int fuse = last ? kFuseNone : fz[p];
+    const bool fold = inverse && last && log_ns > 0 && !fused_in;
     const fe* full = nullptr;
-    if (last && log_ns > 0 && log_n > tw.l16 && log_n >= 17 && log_n <= 26) {
+    if (last && log_ns > 0 && !fused_in && log_n > tw.l16 && log_n >= 17 && log_n <= 26) {
       st = full_table(ctx, tw, lr, fold, stream, &full);
       if (st != STARK_OK) return st;
     }
+    // (A staged producer is never the pass before the last one: a two-pass plan has one column per
+    // r', fuse_modes.  So the inverse's n^-1 rides on the streamed table or on the last pass's own tables.)
     ColTw ct{fold ? tw.d_t16_s : tw.d_t16, tw.d_lo, fold ? tw.d_hi_s : tw.d_hi, full, tw.l16, tw.kb,
-             last ? post : nullptr};
-    const int col = log_ns == 0 ? (sp.skip ? kColSparse : kColNone)
+             last ? post : nullptr, nullptr, nullptr, 0, 0};
+    if (fuse != kFuseNone) {
+      ct.res = tw.d_res[4 + plan.log_r[p + 1]];
+      ct.fused = fuse == kFuseStreamed ? fused_tab : nullptr;
+      ct.log_rp = plan.log_r[p + 1];
+      ct.log_q = log_n - lr - plan.log_r[p + 1];
+    }
+    const int col = (log_ns == 0 || fused_in) ? (sp.skip ? kColSparse : kColNone)
                     : full ? kColFull : log_ns + lr <= tw.l16 ? kColT16 : kColTwoLevel;
     // data image + staged Shoup pairs + digit-basis tables (DbPlan of this instance)
     const size_t image = std::max((size_t)elems, db_full_fe(lr, col));
     const size_t lds = (image + db_lds_fe(lr, col)) * sizeof(fe);
-    hipLaunchKernelGGL(pass_kernel(lr, col), dim3((unsigned)total), dim3(threads), lds, stream, cur, dst, log_n,
+    const pass_fn fn = pass_kernel(lr, col, fuse);
+    if (!fn) return STARK_ERR_BAD_ARG;  // (fuse_modes selects only instances that exist)
+    hipLaunchKernelGGL(fn, dim3((unsigned)total), dim3(threads), lds, stream, cur, dst, log_n,
                        log_ns, lb, ct, tw.d_small + tw.small_off[lr], tw.d_db + tw.db_off[lr], scale,
-                       (inverse && last && !fold) ? 1 : 0, log_tiles, (uint32_t)total, sp);
+                       (inverse && last && !fold && !fused_in) ? 1 : 0, log_tiles, (uint32_t)total, sp);
     STARK_HIP(ctx, hipGetLastError());
     cur = dst;
     log_ns += lr;

@@ -76,6 +76,12 @@ def main():
             torch.cuda.synchronize()
             digests.append(hashlib.sha256(b.cpu().numpy().tobytes()).hexdigest()[:16])
         times = [[] for _ in builds]
+        # One untimed loop per build first: the digests above left the GPU idle, and the first timed loop
+        # after that ran 7 % slow for whichever build came first (clock ramp), which inflated its spread.
+        for (lib, h), b in zip(builds, bufs):
+            for _ in range(a.reps):
+                lib.stark_ntt_dev(h, b.data_ptr(), log_n, batch, root, int(inv), stream.cuda_stream)
+        torch.cuda.synchronize()
         for _ in range(a.rounds):
             for i, ((lib, h), b) in enumerate(zip(builds, bufs)):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -87,7 +93,11 @@ def main():
                 e1.synchronize()
                 times[i].append(e0.elapsed_time(e1) / a.reps)
         out["cases"][case] = {"ms_median": [round(statistics.median(t), 4) for t in times],
-                              "ms_min": [round(min(t), 4) for t in times], "digest": digests,
+                              "ms_min": [round(min(t), 4) for t in times],
+                              # each round's figure (the mean of one timed loop of --reps calls) and their
+                              # max - min, so a build's own round-to-round spread can be read off
+                              "ms_rounds": [[round(v, 4) for v in t] for t in times],
+                              "ms_spread": [round(max(t) - min(t), 4) for t in times], "digest": digests,
                               "digests_equal": len(set(digests)) == 1}
         print(json.dumps({case: out["cases"][case]}), flush=True)
     for lib, h in builds:
