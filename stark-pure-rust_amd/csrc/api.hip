@@ -114,8 +114,8 @@ size_t cache_bytes(const stark_ctx* ctx) {
   size_t b = 0;
   for (const auto& kv : ctx->tw) {
     const size_t full = ((size_t)1 << kv.second->log_n) * sizeof(fe);
-    if (kv.second->d_full) b += full;
-    if (kv.second->d_full_s) b += full;
+    for (const Twiddles::FullSlot& f : kv.second->full)
+      if (f.ptr) b += full;
   }
   for (const auto& kv : ctx->ext_idx) b += kv.second.bytes;
   for (const auto& kv : ctx->post_tw) b += kv.second.bytes;
@@ -127,23 +127,19 @@ bool cache_reserve(stark_ctx* ctx, size_t need, bool evict_ext) {
   bool synced = false;
   for (size_t have = cache_bytes(ctx); have + need > ctx->cache_limit;) {
     // the least recently used candidate
-    fe** full_slot = nullptr;
+    Twiddles::FullSlot* full_slot = nullptr;
     size_t full_bytes = 0;
     auto ext_it = ctx->ext_idx.end();
     uint64_t oldest = UINT64_MAX;
     for (auto& kv : ctx->tw) {
       Twiddles& t = *kv.second;
       const size_t bytes = ((size_t)1 << t.log_n) * sizeof(fe);
-      if (t.d_full && t.full_used < oldest) {
-        oldest = t.full_used;
-        full_slot = &t.d_full;
-        full_bytes = bytes;
-      }
-      if (t.d_full_s && t.full_s_used < oldest) {
-        oldest = t.full_s_used;
-        full_slot = &t.d_full_s;
-        full_bytes = bytes;
-      }
+      for (Twiddles::FullSlot& f : t.full)
+        if (f.ptr && f.used < oldest) {
+          oldest = f.used;
+          full_slot = &f;
+          full_bytes = bytes;
+        }
     }
     if (evict_ext)
       for (auto it = ctx->ext_idx.begin(); it != ctx->ext_idx.end(); ++it)
@@ -169,12 +165,10 @@ bool cache_reserve(stark_ctx* ctx, size_t need, bool evict_ext) {
       synced = true;
     }
     if (full_slot) {
-      hipFree(*full_slot);
-      *full_slot = nullptr;
+      hipFree(full_slot->ptr);
+      full_slot->ptr = nullptr;
+      full_slot->fill = nullptr;  // the victim's fill is complete (synchronised above)
       have -= full_bytes;
-      for (auto& kv : ctx->tw)  // the victim's fill is complete (synchronised above)
-        for (int d = 0; d < 2; ++d)
-          if (full_slot == (d ? &kv.second->d_full_s : &kv.second->d_full)) kv.second->full_fill[d] = nullptr;
     } else if (post_it != ctx->post_tw.end()) {
       hipFree(post_it->second.ptr);
       if (post_it->second.ev) hipEventDestroy(post_it->second.ev);
@@ -318,15 +312,7 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
   hipDeviceSynchronize();  // (work the caller enqueued on its own streams may still read context buffers)
-  for (auto& kv : ctx->tw) {
-    if (kv.second->d_lo) hipFree(kv.second->d_lo);
-    if (kv.second->d_full) hipFree(kv.second->d_full);
-    if (kv.second->d_full_s) hipFree(kv.second->d_full_s);
-    for (uint32_t* r : kv.second->d_res)
-      if (r) hipFree(r);
-    for (hipEvent_t e : kv.second->full_ev)
-      if (e) hipEventDestroy(e);
-  }
+  ctx->tw.clear();  // (~Twiddles frees the tables)
   for (stark_merkle_tree*& t : ctx->trees) {
     stark_merkle_free(t);
     t = nullptr;

@@ -79,21 +79,22 @@ struct Twiddles {
   uint32_t small_off[16] = {0};
   // Full column-twiddle table of the last pass (built on first use when that
   // pass's twiddles do not fit t16): full[c R + r] = w^(c r), c < n/R, r < R;
-  // full_s = full * n^-1 for the inverse.  One product per element instead of
+  // full[1] holds the same times n^-1 for the inverse.  One product per element instead of
   // the two of lo * hi, for one 32-B coalesced read.
-  fe* d_full = nullptr;
-  fe* d_full_s = nullptr;
-  // What each slot holds ([1]: d_full_s): the last pass's log2 radix for the table above, or kFullFused for
-  // the fused producer's per-element table (ntt.hip fused_tw_kernel), which takes its place in a plan whose
-  // last boundary is fused-streamed.  A call that needs the other kind rebuilds the slot.
   static constexpr uint32_t kFullFused = 0x100;
-  uint32_t full_kind[2] = {0, 0};
-  uint64_t full_used = 0, full_s_used = 0;  // cache clock of their last use (LRU eviction, cache_reserve)
-  // The fill of d_full / d_full_s ([1]) is enqueued on the stream of the call that first needs it;
-  // a call on another stream waits for this event until the fill is known to be complete (fill = null).
-  hipEvent_t full_ev[2] = {nullptr, nullptr};
-  hipStream_t full_fill[2] = {nullptr, nullptr};
-  size_t base_bytes = 0;         // device bytes of the tables above d_full (one allocation at d_lo)
+  struct FullSlot {
+    fe* ptr = nullptr;
+    // What the slot holds: the last pass's log2 radix for the table above, or kFullFused for the fused
+    // producer's per-element table (ntt.hip fused_tw_kernel), which takes its place in a plan whose last
+    // boundary is fused-streamed.  A call that needs the other kind rebuilds the slot.
+    uint32_t kind = 0;
+    uint64_t used = 0;  // cache clock of its last use (LRU eviction, cache_reserve)
+    // The fill is enqueued on the stream of the call that first needs the table; a call on another
+    // stream waits for this event until the fill is known to be complete (fill = null).
+    hipEvent_t ev = nullptr;
+    hipStream_t fill = nullptr;
+  } full[2];                     // [1]: the table scaled by n^-1
+  size_t base_bytes = 0;         // device bytes of the tables above `full` (one allocation at d_lo) and of d_res
   size_t n_small_pairs = 0;      // Shoup pairs in d_small
   // Digit-basis tables (fe_db.h) of w_R^k, k < R/2, for every radix R = 2^l >= 16: the constants of the
   // radix-4 steps (ntt.hip DbPlan).  db_off[l] = offset in u32 into d_db (72 u32 per root).
@@ -104,6 +105,21 @@ struct Twiddles {
   uint32_t* d_res[13] = {nullptr};
   HostFp root;      // the root these tables were built for (Montgomery)
   HostFp inv_n;     // n^-1 (Montgomery)
+
+  Twiddles() = default;
+  Twiddles(const Twiddles&) = delete;
+  Twiddles& operator=(const Twiddles&) = delete;
+  // Owns its device memory: the base allocation, the full slots with their events, the residual tables.
+  // (The owner makes sure no kernel still reads them: stark_ctx_destroy synchronises the device first.)
+  ~Twiddles() {
+    if (d_lo) hipFree(d_lo);
+    for (FullSlot& f : full) {
+      if (f.ptr) hipFree(f.ptr);
+      if (f.ev) hipEventDestroy(f.ev);
+    }
+    for (uint32_t* r : d_res)
+      if (r) hipFree(r);
+  }
 };
 
 // A cached device buffer with the cache clock of its last use.
@@ -112,7 +128,7 @@ struct CacheBuf {
   size_t bytes = 0;
   uint64_t used = 0;
   bool in_use = false;          // held by a call in progress: never evicted (cache_reserve)
-  hipEvent_t ev = nullptr;      // the fill's event while it may still run (stream `fill`), as Twiddles::full_ev
+  hipEvent_t ev = nullptr;      // the fill's event while it may still run (stream `fill`), as Twiddles::FullSlot::ev
   hipStream_t fill = nullptr;
 };
 

@@ -16,6 +16,9 @@
 // the last pass's store.
 #include <stdlib.h>
 
+#include <algorithm>
+#include <utility>
+
 #include "fe_db.h"
 #include "internal.h"
 
@@ -40,22 +43,11 @@ struct ColTw {
 // One Stockham pass (see the file comment): each workgroup transforms one tile of B adjacent
 // columns x R points.  T = B*R/4 threads, each owning exactly 4 elements in every phase.
 
-// Two independent Montgomery products interleaved in one asm block (the full-table and two-level
-// column twiddles).  Shoup products stay one chain per block: the interleaved pair measured 1.867 vs
-// 1.843 ms per 2^24 transform.
-__device__ __forceinline__ void shoup2(fe& r, fe& s, const fe& a, const fe& w, const fe& wq, const fe& c,
-                                       const fe& x, const fe& xq) {
-  r = fe_mul_shoup(a, w, wq);
-  s = fe_mul_shoup(c, x, xq);
-}
-__device__ __forceinline__ void mul2(fe& r, fe& s, const fe& a, const fe& b, const fe& c, const fe& d) {
-  fe_mul_lazy2(r, s, a, b, c, d);
-}
-
-// fe_bfly_lazy for an X input already below 2p (a product or a canonical load): no reduction of X.
-__device__ __forceinline__ void bfly_lt2p(fe& x, fe& y, const fe& t) {
-  fe_bfly_lazy_reduced(x, y, t);
-}
+// Products: the full-table and two-level column twiddles are two independent Montgomery products
+// interleaved in one asm block (fe_mul_lazy2).  Shoup products (fe_mul_shoup) stay one chain per block:
+// the interleaved pair measured 1.867 vs 1.843 ms per 2^24 transform.
+// Butterflies: fe_bfly_lazy_reduced is fe_bfly_lazy for an X input already below 2p (a product or a
+// canonical load): no reduction of X.
 
 // The pass's lazy range is [0, 4p + 2^224) (4p + 2^224 < 2^256: top word 0xc19139cb).
 // csub2p_top: x <- x - 2p when x's top word is above 2p's (so x > 2p), a branch over the 8-word
@@ -317,8 +309,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
         for (int t = 0; t < 4; ++t) tw[t] = fe_load_nt(ct.full + ((((j0 + eb[t]) & ns_mask) << LOG_R) + er[t]));
         // Montgomery images (the table streams from HBM once per transform, so it stays 32 B per
         // entry): v < 4p, tw < p -> [0, 2p); two interleaved products per block
-        mul2(v[0], v[1], v[0], tw[0], v[1], tw[1]);
-        mul2(v[2], v[3], v[2], tw[2], v[3], tw[3]);
+        fe_mul_lazy2(v[0], v[1], v[0], tw[0], v[1], tw[1]);
+        fe_mul_lazy2(v[2], v[3], v[2], tw[2], v[3], tw[3]);
       } else if (COL == kColT16) {
         // Shoup pairs from the L2-resident t16 table: v < 2^256 -> [0, 2p)
         const fe* e[4];
@@ -327,8 +319,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
           const uint64_t k = ((uint64_t)((j0 + eb[t]) & ns_mask) * er[t]) & (((uint64_t)1 << lnr) - 1);
           e[t] = ct.t16 + 2 * (k << (ct.l16 - lnr));
         }
-        shoup2(v[0], v[1], v[0], e[0][0], e[0][1], v[1], e[1][0], e[1][1]);
-        shoup2(v[2], v[3], v[2], e[2][0], e[2][1], v[3], e[3][0], e[3][1]);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = fe_mul_shoup(v[t], e[t][0], e[t][1]);
       } else {
         const uint32_t unit = log_n - lnr;
 #pragma unroll
@@ -336,8 +328,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
           const uint64_t ex = ((uint64_t)((j0 + eb[t]) & ns_mask) * er[t]) << unit;
           tw[t] = fe_mul(ct.lo[ex & (((uint64_t)1 << ct.kb) - 1)], ct.hi[ex >> ct.kb]);
         }
-        mul2(v[0], v[1], v[0], tw[0], v[1], tw[1]);
-        mul2(v[2], v[3], v[2], tw[2], v[3], tw[3]);
+        fe_mul_lazy2(v[0], v[1], v[0], tw[0], v[1], tw[1]);
+        fe_mul_lazy2(v[2], v[3], v[2], tw[2], v[3], tw[3]);
       }
     }
     if (sp.skip == 0) {
@@ -347,8 +339,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       // Its inputs are below 2p (canonical loads, or column-twiddle products in [0, 2p)), so the first
       // butterflies need no reductions.
       if ((LOG_R & 1) == 0) {  // x0..x3 = v[0], v[2], v[1], v[3]
-        bfly_lt2p(v[0], v[2], v[2]);
-        bfly_lt2p(v[1], v[3], v[3]);
+        fe_bfly_lazy_reduced(v[0], v[2], v[2]);
+        fe_bfly_lazy_reduced(v[1], v[3], v[3]);
         fe t3;
         if (DB::on) {
           t3 = fe_mul_db(v[3], db + 72u * (1u << (LOG_R - 2)));  // w_4^1 = w_R^(R/4), wave-uniform: SGPRs
@@ -360,8 +352,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
         bfly<FAST>(v[0], v[1], v[1]);
         bfly<FAST>(v[2], v[3], t3);
       } else {
-        bfly_lt2p(v[0], v[2], v[2]);
-        bfly_lt2p(v[1], v[3], v[3]);
+        fe_bfly_lazy_reduced(v[0], v[2], v[2]);
+        fe_bfly_lazy_reduced(v[1], v[3], v[3]);
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -381,16 +373,13 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
   }
   // A streamed producer's four merged twiddles ([tile][kk][tid]: 8 KB contiguous per kk), issued after
   // the jj-major step's barrier, where that step's registers are free (165 VGPRs).  Issued before it
-  // (STARK_FUSED_TW_EARLY, so that they fly during the step) the pass spills 38 VGPRs.
+  // (so that they fly during the step) the pass spills 38 VGPRs and measured the same.
   fe ftw[4];
   auto load_ftw = [&]() {
     const fe* f = ct.fused + ((size_t)(tile & tile_mask) << (LOG_R + log_b)) + tid;
 #pragma unroll
     for (int k = 0; k < 4; ++k) ftw[k] = fe_load_nt(f + (uint32_t)k * nthr);
   };
-#ifdef STARK_FUSED_TW_EARLY
-  if (FUSE == kFuseStreamed && active) load_ftw();
-#endif
   __syncthreads();
 
   // ---- R-point DIT over the bit-reversed image ----
@@ -459,7 +448,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
         fe t1, t3;
         const uint32_t ia = 2 * (jj << (LOG_R - 1 - kS0));
         const fe ta = sm[ia], taq = sm[ia + 1];
-        shoup2(t1, t3, x1, ta, taq, x3, ta, taq);
+        t1 = fe_mul_shoup(x1, ta, taq);
+        t3 = fe_mul_shoup(x3, ta, taq);
         bfly<FAST>(x0, x1, t1);
         bfly<FAST>(x2, x3, t3);
         const uint32_t ic = 2 * ((jj + (1u << kS0)) << (LOG_R - 2 - kS0));
@@ -476,9 +466,7 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       XI.st(i0 + 3 * st, x3);
     }
     __syncthreads();
-#ifndef STARK_FUSED_TW_EARLY
     if (FUSE == kFuseStreamed && active) load_ftw();
-#endif
     s = kS0 + 2;
   }
   // ---- radix 2^8 / 2^7 as T x 16 (DbPlan::four): twiddles, then a 16-point DFT across the groups ----
@@ -500,8 +488,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       const bool unit0 = FUSE == kFuseNone && ((64u >> log_b) <= (1u << LT) ? __builtin_amdgcn_readfirstlane(a) : a) == 0;
       if (FUSE == kFuseStreamed) {
         const fe v0 = XI.ld(i0), v1 = XI.ld(i0 + st), v2 = XI.ld(i0 + 2 * st), v3 = XI.ld(i0 + 3 * st);
-        mul2(x[0], x[1], v0, ftw[0], v1, ftw[1]);  // [0, 4p) x Montgomery image -> [0, 2p)
-        mul2(x[2], x[3], v2, ftw[2], v3, ftw[3]);
+        fe_mul_lazy2(x[0], x[1], v0, ftw[0], v1, ftw[1]);  // [0, 4p) x Montgomery image -> [0, 2p)
+        fe_mul_lazy2(x[2], x[3], v2, ftw[2], v3, ftw[3]);
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -522,8 +510,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       }
       // 16-point DFT across the groups, first radix-4 step (stride 16 rows): only w_4 (SGPRs); the
       // twiddled inputs are below 2p
-      bfly_lt2p(x[0], x[1], x[1]);
-      bfly_lt2p(x[2], x[3], x[3]);
+      fe_bfly_lazy_reduced(x[0], x[1], x[1]);
+      fe_bfly_lazy_reduced(x[2], x[3], x[3]);
       const fe t3 = fe_mul_db(x[3], db + 72u * (1u << (LOG_R - 2)));
       fe_csub2p(x[2]);
       bfly<FAST>(x[0], x[2], x[2]);
@@ -547,7 +535,7 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
           bfly<FAST>(x0, x2, x2);
           bfly<FAST>(x1, x3, t3);
         } else {
-          const uint32_t* wa = db + 72u * (a << (LOG_R - 3));  // w_8^a = w_R^(a R/8)
+          const uint32_t* wa = db + 72u * (a << (LT + 1));  // w_8^a = w_R^(a R/8), R/8 = 2 T
           const fe t1 = fe_mul_db(x1, wa);
           fe t3 = fe_mul_db(x3, wa);
           bfly<FAST>(x0, x1, t1);
@@ -632,7 +620,8 @@ __global__ __launch_bounds__(kPassThreads, (DbPlan<LOG_R, COL>::occupancy)) void
       fe t1, t3;
       const uint32_t ia = 2 * (jj << (LOG_R - 1 - s));  // w_{2m}^jj, Shoup pairs staged in LDS
       const fe ta = sm[ia], taq = sm[ia + 1];
-      shoup2(t1, t3, x1, ta, taq, x3, ta, taq);
+      t1 = fe_mul_shoup(x1, ta, taq);
+      t3 = fe_mul_shoup(x3, ta, taq);
       bfly<FAST>(x0, x1, t1);  // (y0, y1)
       bfly<FAST>(x2, x3, t3);  // (y2, y3)
       const uint32_t ic = 2 * ((jj + m) << (LOG_R - 2 - s));  // w_{4m}^(jj+m)
@@ -828,81 +817,43 @@ uint32_t choose_log_b_impl(uint32_t log_n, uint32_t log_r, uint32_t tile_log) {
 typedef void (*pass_fn)(const fe*, fe*, uint32_t, uint32_t, uint32_t, ColTw, const fe*, const uint32_t*, fe, int,
                         uint32_t, uint32_t, Sparse);
 
-// Minimum data-image size of a pass instance (in fe): the last-step table is staged over it.
-template <int COL>
-size_t db_full_fe_c(uint32_t log_r) {
-  switch (log_r) {
-    case 4: return DbPlan<4, COL>::full_fe;
-    case 5: return DbPlan<5, COL>::full_fe;
-    case 6: return DbPlan<6, COL>::full_fe;
-    case 7: return DbPlan<7, COL>::full_fe;
-    case 8: return DbPlan<8, COL>::full_fe;
-    default: return 0;
-  }
+// A kernel instance and its LDS needs (DbPlan), in fe:
+//   full_fe: minimum size of the data image (the last step's digit-basis table is staged over it);
+//   extra_fe: what precedes the image, staged Shoup pairs + digit-basis tables.
+struct PassInstance {
+  pass_fn fn;
+  uint32_t full_fe;
+  uint32_t extra_fe;
+};
+template <int LOG_R, int COL, int FUSE = kFuseNone>
+constexpr PassInstance make_instance() {
+  using DB = DbPlan<LOG_R, COL>;
+  return {ntt_pass_kernel<LOG_R, COL, FUSE>, DB::full_fe, DB::lds_fe + DB::shoup_fe};
 }
-size_t db_full_fe(uint32_t log_r, int col) {
-  switch (col) {
-    case kColNone: return db_full_fe_c<kColNone>(log_r);
-    case kColSparse: return db_full_fe_c<kColSparse>(log_r);
-    case kColFull: return db_full_fe_c<kColFull>(log_r);
-    case kColT16: return db_full_fe_c<kColT16>(log_r);
-    default: return db_full_fe_c<kColTwoLevel>(log_r);
-  }
-}
-
-// LDS of a pass instance beyond its data image: staged Shoup pairs + digit-basis tables (in fe).
-template <int COL>
-size_t db_lds_fe_c(uint32_t log_r) {
-  switch (log_r) {
-    case 4: return DbPlan<4, COL>::lds_fe + DbPlan<4, COL>::shoup_fe;
-    case 5: return DbPlan<5, COL>::lds_fe + DbPlan<5, COL>::shoup_fe;
-    case 6: return DbPlan<6, COL>::lds_fe + DbPlan<6, COL>::shoup_fe;
-    case 7: return DbPlan<7, COL>::lds_fe + DbPlan<7, COL>::shoup_fe;
-    case 8: return DbPlan<8, COL>::lds_fe + DbPlan<8, COL>::shoup_fe;
-    case 9: return DbPlan<9, COL>::lds_fe + DbPlan<9, COL>::shoup_fe;
-    default: return (size_t)1 << log_r;
-  }
-}
-size_t db_lds_fe(uint32_t log_r, int col) {
-  switch (col) {
-    case kColNone: return db_lds_fe_c<kColNone>(log_r);
-    case kColSparse: return db_lds_fe_c<kColSparse>(log_r);
-    case kColFull: return db_lds_fe_c<kColFull>(log_r);
-    case kColT16: return db_lds_fe_c<kColT16>(log_r);
-    default: return db_lds_fe_c<kColTwoLevel>(log_r);
-  }
+// A radix's row of the table lists the sources in the order the kernels have always been emitted in, which
+// keeps the code object as it was.
+constexpr int kRowCol[5] = {kColNone, kColSparse, kColFull, kColT16, kColTwoLevel};
+template <int... I>
+const PassInstance* unfused_instances(std::integer_sequence<int, I...>) {
+  static const PassInstance t[] = {make_instance<2 + I / 5, kRowCol[I % 5]>()...};
+  return t;
 }
 
-template <int LOG_R>
-pass_fn pass_kernel_r(int col) {
-  switch (col) {
-    case kColNone: return ntt_pass_kernel<LOG_R, kColNone>;
-    case kColSparse: return ntt_pass_kernel<LOG_R, kColSparse>;
-    case kColFull: return ntt_pass_kernel<LOG_R, kColFull>;
-    case kColT16: return ntt_pass_kernel<LOG_R, kColT16>;
-    default: return ntt_pass_kernel<LOG_R, kColTwoLevel>;
+// Every instance there is: the three fused producers (radix 2^8, dense; fuse_modes selects nothing else),
+// and radices 2^2..2^9 with each column-twiddle source.  fn is null where there is none.
+PassInstance pass_instance(uint32_t log_r, int col, int fuse = kFuseNone) {
+  if (fuse != kFuseNone) {
+    if (log_r == 8 && fuse == kFuseStaged && col == kColNone) return make_instance<8, kColNone, kFuseStaged>();
+    if (log_r == 8 && fuse == kFuseStreamed && col == kColT16) return make_instance<8, kColT16, kFuseStreamed>();
+    if (log_r == 8 && fuse == kFuseStreamed && col == kColNone) return make_instance<8, kColNone, kFuseStreamed>();
+    return {nullptr, 0, 0};
   }
-}
-
-pass_fn pass_kernel(uint32_t log_r, int col, int fuse = kFuseNone) {
-  if (fuse != kFuseNone) {  // radix 2^8, dense (ntt_device_plan selects nothing else)
-    if (log_r != 8) return nullptr;
-    if (fuse == kFuseStaged) return col == kColNone ? ntt_pass_kernel<8, kColNone, kFuseStaged> : nullptr;
-    return col == kColNone  ? ntt_pass_kernel<8, kColNone, kFuseStreamed>
-           : col == kColT16 ? ntt_pass_kernel<8, kColT16, kFuseStreamed>
-                            : nullptr;
-  }
-  switch (log_r) {
-    case 2: return pass_kernel_r<2>(col);
-    case 3: return pass_kernel_r<3>(col);
-    case 4: return pass_kernel_r<4>(col);
-    case 5: return pass_kernel_r<5>(col);
-    case 6: return pass_kernel_r<6>(col);
-    case 7: return pass_kernel_r<7>(col);
-    case 8: return pass_kernel_r<8>(col);
-    case 9: return pass_kernel_r<9>(col);
-    default: return nullptr;
-  }
+  if (log_r < 2 || log_r > kMaxLogR) return {nullptr, 0, 0};
+  // Row log_r - 2 of the table, entry i of the row where kRowCol[i] is the source asked for.
+  static const PassInstance* t = unfused_instances(std::make_integer_sequence<int, (kMaxLogR - 1) * 5>());
+  for (int i = 0; i < 5; ++i)
+    if (kRowCol[i] == col) return t[(log_r - 2) * 5 + i];
+  return {nullptr, 0, 0};
 }
 
 // Fusion policy of a transform (ntt_pass_kernel FUSE): the size's own choice, or a test's.
@@ -959,6 +910,27 @@ static stark_status ntt_device_plan(stark_ctx* ctx, const fe* src, uint32_t zero
                                     uint32_t batch, const Twiddles& tw, bool inverse, hipStream_t stream,
                                     const fe* post, const PassPlan& plan, int policy, uint32_t* used = nullptr);
 
+// Appends scale * base^i, i < count, to h (scale: 1 when null), each as a Montgomery image (1 fe), a
+// Shoup pair (shoup_pair, 2 fe) or a digit-basis table (db_table, 72 u32 = 9 fe).
+enum TableForm { kPlain, kShoup, kDigitBasis };
+static void push_powers(std::vector<fe>& h, const HostFp& base, size_t count, TableForm form,
+                        const HostFp* scale = nullptr) {
+  const FieldHost& F = FieldHost::get();
+  const size_t entry_fe = form == kPlain ? 1 : form == kShoup ? 2 : 9;
+  size_t at = h.size();
+  h.resize(at + entry_fe * count);
+  HostFp a = scale ? *scale : F.one();
+  for (size_t i = 0; i < count; ++i, at += entry_fe) {
+    if (form == kPlain)
+      h[at] = to_dev(a);
+    else if (form == kShoup)
+      shoup_pair(a, &h[at]);
+    else
+      db_table(a, reinterpret_cast<uint32_t*>(&h[at]));  // (the entry's 9 fe as 72 words)
+    a = F.mul(a, base);
+  }
+}
+
 stark_status get_twiddles(stark_ctx* ctx, const uint64_t root[4], uint32_t log_n, const Twiddles** out) {
   const FieldHost& F = FieldHost::get();
   if (log_n > 28) return STARK_ERR_BAD_LENGTH;  // 2-adicity of BN254 Fr
@@ -983,120 +955,59 @@ stark_status get_twiddles(stark_ctx* ctx, const uint64_t root[4], uint32_t log_n
   tw->kb = (log_n + 1) / 2;
   tw->root = w;
   tw->inv_n = F.inv(F.from_u64((uint64_t)1 << log_n));
-  const size_t n_lo = (size_t)1 << tw->kb, n_hi = (size_t)1 << (log_n - tw->kb);
-  std::vector<fe> h_lo(n_lo), h_hi(n_hi);
-  HostFp acc = F.one();
-  for (size_t i = 0; i < n_lo; ++i) {
-    h_lo[i] = to_dev(acc);
-    acc = F.mul(acc, w);
-  }
-  const HostFp step = acc;  // w^(2^kb)
-  acc = F.one();
-  for (size_t i = 0; i < n_hi; ++i) {
-    h_hi[i] = to_dev(acc);
-    acc = F.mul(acc, step);
-  }
-  // Small-root tables for every radix 2^l (l <= min(log_n, 9)): w^(k n / R), k < R/2 (k < R for
-  // R = 2^8: the 16 x 16 passes' twiddles, DbPlan::four).
-  std::vector<fe> h_small;
-  for (uint32_t l = 1; l <= kMaxLogR && l <= log_n; ++l) {
-    tw->small_off[l] = (uint32_t)h_small.size();
-    const HostFp wr = F.pow_u64(w, (uint64_t)1 << (log_n - l));
-    HostFp a = F.one();
-    for (uint32_t k = 0; k < ((l == 7 || l == 8) ? (1u << l) : (1u << (l - 1))); ++k) {
-      fe pr[2];
-      shoup_pair(a, pr);
-      h_small.push_back(pr[0]);
-      h_small.push_back(pr[1]);
-      a = F.mul(a, wr);
-    }
-  }
-  if (h_small.empty()) {
-    fe pr[2];
-    shoup_pair(F.one(), pr);
-    h_small.push_back(pr[0]);
-    h_small.push_back(pr[1]);
-  }
   // t16[i] = w^(i n / 2^l16): the w_{Ns R} powers of every pass with Ns R <= 2^l16
   // (2^16 entries; 2^18 from 2^25 on, where the middle pass of radix 2^9 has Ns R = 2^17 / 2^18).
   tw->l16 = log_n >= 25 ? 18 : (log_n < 16 ? log_n : 16);
-  const size_t n16 = (size_t)1 << tw->l16;
-  std::vector<fe> h_t16(2 * n16);
-  {
-    const HostFp w16 = F.pow_u64(w, (uint64_t)1 << (log_n - tw->l16));
-    HostFp a = F.one();
-    for (size_t i = 0; i < n16; ++i) {
-      shoup_pair(a, &h_t16[2 * i]);
-      a = F.mul(a, w16);
-    }
+  const size_t n_lo = (size_t)1 << tw->kb, n_hi = (size_t)1 << (log_n - tw->kb), n16 = (size_t)1 << tw->l16;
+  const HostFp w_hi = F.pow_u64(w, (uint64_t)1 << tw->kb), w16 = F.pow_u64(w, (uint64_t)1 << (log_n - tw->l16));
+  // Every table in one host buffer, in the order of the device allocation.
+  std::vector<fe> h;
+  push_powers(h, w, n_lo, kPlain);
+  const size_t o_hi = h.size();
+  push_powers(h, w_hi, n_hi, kPlain);
+  // Small-root tables for every radix 2^l (l <= min(log_n, 9)): w^(k n / R), k < R/2 (k < R for
+  // R = 2^7, 2^8: the T x 16 passes' twiddles, DbPlan::four).
+  const size_t o_small = h.size();
+  for (uint32_t l = 1; l <= kMaxLogR && l <= log_n; ++l) {
+    tw->small_off[l] = (uint32_t)(h.size() - o_small);
+    push_powers(h, F.pow_u64(w, (uint64_t)1 << (log_n - l)), (l == 7 || l == 8) ? (1u << l) : (1u << (l - 1)), kShoup);
   }
+  if (h.size() == o_small) push_powers(h, F.one(), 1, kShoup);
+  tw->n_small_pairs = (h.size() - o_small) / 2;
+  const size_t o_t16 = h.size();
+  push_powers(h, w16, n16, kShoup);
   // Copies scaled by n^-1: the inverse's last pass multiplies every element by
   // a column twiddle anyway, so folding n^-1 into it makes the scale free.
-  std::vector<fe> h_hi_s(n_hi), h_t16_s(2 * n16);
-  {
-    HostFp a = F.one();
-    const HostFp step_hi = F.pow_u64(w, (uint64_t)1 << tw->kb);
-    for (size_t i = 0; i < n_hi; ++i) {
-      h_hi_s[i] = to_dev(F.mul(a, tw->inv_n));
-      a = F.mul(a, step_hi);
-    }
-    const HostFp w16 = F.pow_u64(w, (uint64_t)1 << (log_n - tw->l16));
-    a = F.one();
-    for (size_t i = 0; i < n16; ++i) {
-      shoup_pair(F.mul(a, tw->inv_n), &h_t16_s[2 * i]);
-      a = F.mul(a, w16);
-    }
-  }
-  tw->n_small_pairs = h_small.size() / 2;
+  const size_t o_hi_s = h.size();
+  push_powers(h, w_hi, n_hi, kPlain, &tw->inv_n);
+  const size_t o_t16_s = h.size();
+  push_powers(h, w16, n16, kShoup, &tw->inv_n);
   // Digit-basis tables: w_R^k, k < R/2, for R = 2^l, 1 <= l <= min(log_n, 9) (a pass stages every
   // stride-th one, DbPlan; the distributed NTT's cross-rank DFTs use l <= 3, dist.hip).
-  std::vector<uint32_t> h_db;
+  const size_t o_db = h.size();
   for (uint32_t l = 1; l <= kMaxLogR && l <= log_n; ++l) {
-    tw->db_off[l] = (uint32_t)h_db.size();
-    const HostFp wr = F.pow_u64(w, (uint64_t)1 << (log_n - l));
-    HostFp a = F.one();
-    for (uint32_t k = 0; k < (1u << (l - 1)); ++k) {
-      uint32_t t[72];
-      db_table(a, t);
-      h_db.insert(h_db.end(), t, t + 72);
-      a = F.mul(a, wr);
-    }
+    tw->db_off[l] = (uint32_t)((h.size() - o_db) * 8);  // in u32
+    push_powers(h, F.pow_u64(w, (uint64_t)1 << (log_n - l)), 1u << (l - 1), kDigitBasis);
   }
-  if (h_db.empty()) h_db.resize(72, 0);
-  const size_t db_fe = h_db.size() / 8;  // 72 u32 = 9 fe per constant
-  const size_t bytes = (n_lo + 2 * n_hi + h_small.size() + 4 * n16 + db_fe) * sizeof(fe);
+  if (h.size() == o_db) h.resize(o_db + 9);  // (one all-zero constant)
   void* d = nullptr;
-  if (hipMalloc(&d, bytes) != hipSuccess) return STARK_ERR_OOM;
-  tw->d_lo = (fe*)d;
-  tw->d_hi = tw->d_lo + n_lo;
-  tw->d_small = tw->d_hi + n_hi;
-  tw->d_t16 = tw->d_small + h_small.size();
-  tw->d_hi_s = tw->d_t16 + 2 * n16;
-  tw->d_t16_s = tw->d_hi_s + n_hi;
-  tw->d_db = reinterpret_cast<uint32_t*>(tw->d_t16_s + 2 * n16);
-  tw->base_bytes = bytes;
-  STARK_HIP(ctx, hipMemcpy(tw->d_lo, h_lo.data(), n_lo * sizeof(fe), hipMemcpyHostToDevice));
-  STARK_HIP(ctx, hipMemcpy(tw->d_hi, h_hi.data(), n_hi * sizeof(fe), hipMemcpyHostToDevice));
-  STARK_HIP(ctx, hipMemcpy(tw->d_small, h_small.data(), h_small.size() * sizeof(fe), hipMemcpyHostToDevice));
-  STARK_HIP(ctx, hipMemcpy(tw->d_t16, h_t16.data(), 2 * n16 * sizeof(fe), hipMemcpyHostToDevice));
-  STARK_HIP(ctx, hipMemcpy(tw->d_hi_s, h_hi_s.data(), n_hi * sizeof(fe), hipMemcpyHostToDevice));
-  STARK_HIP(ctx, hipMemcpy(tw->d_t16_s, h_t16_s.data(), 2 * n16 * sizeof(fe), hipMemcpyHostToDevice));
-  STARK_HIP(ctx, hipMemcpy(tw->d_db, h_db.data(), h_db.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (hipMalloc(&d, h.size() * sizeof(fe)) != hipSuccess) return STARK_ERR_OOM;
+  tw->d_lo = (fe*)d;  // (from here on ~Twiddles frees it on every error path)
+  tw->d_hi = tw->d_lo + o_hi;
+  tw->d_small = tw->d_lo + o_small;
+  tw->d_t16 = tw->d_lo + o_t16;
+  tw->d_hi_s = tw->d_lo + o_hi_s;
+  tw->d_t16_s = tw->d_lo + o_t16_s;
+  tw->d_db = reinterpret_cast<uint32_t*>(tw->d_lo + o_db);
+  tw->base_bytes = h.size() * sizeof(fe);
+  STARK_HIP(ctx, hipMemcpy(tw->d_lo, h.data(), h.size() * sizeof(fe), hipMemcpyHostToDevice));
   // Residual tables of the boundaries this size's plan fuses.
   if (log_n >= 2) {
     const PassPlan plan = plan_passes(log_n);
     int fz[8];
     fuse_modes(plan, log_n, tw->l16, kFuseAuto, true, fz);
     for (int p = 0; p + 1 < plan.n_pass; ++p)
-      if (fz[p] != kFuseNone) {
-        const stark_status st = res_table(ctx, *tw, 4 + plan.log_r[p + 1]);
-        if (st != STARK_OK) {
-          for (uint32_t* r : tw->d_res)
-            if (r) hipFree(r);
-          hipFree(tw->d_lo);
-          return st;
-        }
-      }
+      if (fz[p] != kFuseNone) STARK_TRY(res_table(ctx, *tw, 4 + plan.log_r[p + 1]));
   }
   *out = tw.get();
   ctx->tw.emplace(key, std::move(tw));
@@ -1145,16 +1056,15 @@ __global__ void fused_tw_kernel(const fe* __restrict__ lo, const fe* __restrict_
 static stark_status full_table(stark_ctx* ctx, const Twiddles& tw_c, uint32_t kind, bool scaled, hipStream_t stream,
                                const fe** out) {
   Twiddles& tw = const_cast<Twiddles&>(tw_c);  // lazily filled cache entry
-  fe*& slot = scaled ? tw.d_full_s : tw.d_full;
-  const int d = scaled ? 1 : 0;
-  (scaled ? tw.full_s_used : tw.full_used) = ++ctx->cache_clock;
-  if (slot && tw.full_kind[d] != kind) {
+  Twiddles::FullSlot& slot = tw.full[scaled ? 1 : 0];
+  slot.used = ++ctx->cache_clock;
+  if (slot.ptr && slot.kind != kind) {
     STARK_HIP(ctx, hipDeviceSynchronize());  // (a kernel of any stream may still read it)
-    hipFree(slot);
-    slot = nullptr;
-    tw.full_fill[d] = nullptr;
+    hipFree(slot.ptr);
+    slot.ptr = nullptr;
+    slot.fill = nullptr;
   }
-  if (!slot) {
+  if (!slot.ptr) {
     const uint64_t n = (uint64_t)1 << tw.log_n;
     void* p = nullptr;
     if (!cache_reserve(ctx, n * sizeof(fe), false) || hipMalloc(&p, n * sizeof(fe)) != hipSuccess) {
@@ -1171,13 +1081,13 @@ static stark_status full_table(stark_ctx* ctx, const Twiddles& tw_c, uint32_t ki
     STARK_HIP(ctx, hipGetLastError());
     // Published now, complete only when the fill has run on `stream`: a call on another stream
     // waits for this event (fill_wait below) instead of reading a table still being written.
-    STARK_TRY(fill_mark(ctx, tw.full_ev[d], tw.full_fill[d], stream));
-    slot = (fe*)p;
-    tw.full_kind[d] = kind;
+    STARK_TRY(fill_mark(ctx, slot.ev, slot.fill, stream));
+    slot.ptr = (fe*)p;
+    slot.kind = kind;
   } else {
-    STARK_TRY(fill_wait(ctx, tw.full_ev[d], tw.full_fill[d], stream));
+    STARK_TRY(fill_wait(ctx, slot.ev, slot.fill, stream));
   }
-  *out = slot;
+  *out = slot.ptr;
   return STARK_OK;
 }
 
@@ -1267,6 +1177,47 @@ stark_status ntt_device_from(stark_ctx* ctx, const fe* src, uint32_t zero_log, f
                          log_n >= 2 ? plan_passes(log_n) : PassPlan(), kFuseAuto);
 }
 
+// A pass's column-twiddle tables: those scaled by n^-1 when `fold` (an inverse's last pass).  The caller
+// adds the full table, the post factors and, for a fused producer, the fused fields.
+static ColTw col_tw(const Twiddles& tw, bool fold) {
+  ColTw ct{};
+  ct.t16 = fold ? tw.d_t16_s : tw.d_t16;
+  ct.lo = tw.d_lo;
+  ct.hi = fold ? tw.d_hi_s : tw.d_hi;
+  ct.l16 = tw.l16;
+  ct.kb = tw.kb;
+  return ct;
+}
+
+// A first pass of radix 2^lr over an input whose rows >= R >> zero_log are zero.  Copy stages the pass's
+// stage pairing can skip: odd radices run a radix-2 stage 0 then pairs (1,2), (3,4)..; even ones pairs (0,1)..
+static Sparse sparse_first(uint32_t zero_log, uint32_t lr, uint32_t log_n) {
+  uint32_t k = zero_log < lr ? zero_log : lr;
+  if ((k & 1) != (lr & 1)) --k;
+  return Sparse{k, zero_log, log_n - zero_log};
+}
+
+// One pass of radix 2^lr over `batch` transforms: the tile geometry, the instance of (lr, col, fuse) with
+// its LDS (data image + staged Shoup pairs + digit-basis tables, DbPlan), and the launch.
+static stark_status launch_pass(stark_ctx* ctx, hipStream_t stream, const Twiddles& tw, const fe* in, fe* out,
+                                uint32_t log_n, uint32_t log_ns, uint32_t lr, uint32_t batch, int col, int fuse,
+                                const ColTw& ct, int do_scale, const Sparse& sp) {
+  const PassInstance pi = pass_instance(lr, col, fuse);
+  if (!pi.fn) return STARK_ERR_BAD_ARG;  // (fuse_modes selects only instances that exist)
+  const uint32_t lb = choose_log_b_impl(log_n, lr, kTileLog);
+  const uint32_t elems = 1u << (lr + lb);
+  const uint32_t threads = elems / 4 < 64 ? 64 : elems / 4;
+  const uint32_t log_tiles = log_n - lr - lb;
+  const uint64_t total = (uint64_t)batch << log_tiles;
+  const size_t image = std::max((size_t)elems, (size_t)pi.full_fe);
+  const size_t lds = (image + pi.extra_fe) * sizeof(fe);
+  hipLaunchKernelGGL(pi.fn, dim3((unsigned)total), dim3(threads), lds, stream, in, out, log_n, log_ns, lb, ct,
+                     tw.d_small + tw.small_off[lr], tw.d_db + tw.db_off[lr], to_dev(tw.inv_n), do_scale, log_tiles,
+                     (uint32_t)total, sp);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
 // The transform by a given pass plan (ntt_device_from: the size's own) and fusion policy.
 static stark_status ntt_device_plan(stark_ctx* ctx, const fe* src, uint32_t zero_log, fe* d_data, uint32_t log_n,
                                     uint32_t batch, const Twiddles& tw, bool inverse, hipStream_t stream,
@@ -1325,19 +1276,7 @@ static stark_status ntt_device_plan(stark_ctx* ctx, const fe* src, uint32_t zero
     // Passes before the last ping-pong; the last pass (Ns R = n) reads and
     // writes the same positions, so it always lands in d_data.
     fe* dst = last ? d_data : (cur == d_data ? scratch : d_data);
-    Sparse sp{0, 0, log_n};
-    if (p == 0 && src) {
-      // Copy stages the pass's stage pairing can skip: odd radices run a
-      // radix-2 stage 0 then pairs (1,2), (3,4)..; even ones pairs (0,1)..
-      uint32_t k = zero_log < lr ? zero_log : lr;
-      if ((k & 1) != (lr & 1)) --k;
-      sp = Sparse{k, zero_log, log_n - zero_log};
-    }
-    const uint32_t lb = choose_log_b_impl(log_n, lr, kTileLog);
-    const uint32_t elems = 1u << (lr + lb);
-    const uint32_t threads = elems / 4 < 64 ? 64 : elems / 4;
-    const uint32_t log_tiles = log_n - lr - lb;
-    const uint64_t total = (uint64_t)batch << log_tiles;
+    const Sparse sp = (p == 0 && src) ? sparse_first(zero_log, lr, log_n) : Sparse{0, 0, log_n};
     // Inverse: n^-1 rides on the last pass's column twiddles (scaled tables)
     // when that pass has them (log_ns > 0), else it is an explicit product.
     // A pass after a fused boundary has no column twiddle (the producer applied it, with the inverse's
@@ -1352,8 +1291,9 @@ static stark_status ntt_device_plan(stark_ctx* ctx, const fe* src, uint32_t zero
     }
     // (A staged producer is never the pass before the last one: a two-pass plan has one column per
     // r', fuse_modes.  So the inverse's n^-1 rides on the streamed table or on the last pass's own tables.)
-    ColTw ct{fold ? tw.d_t16_s : tw.d_t16, tw.d_lo, fold ? tw.d_hi_s : tw.d_hi, full, tw.l16, tw.kb,
-             last ? post : nullptr, nullptr, nullptr, 0, 0};
+    ColTw ct = col_tw(tw, fold);
+    ct.full = full;
+    ct.post = last ? post : nullptr;
     if (fuse != kFuseNone) {
       ct.res = tw.d_res[4 + plan.log_r[p + 1]];
       ct.fused = fuse == kFuseStreamed ? fused_tab : nullptr;
@@ -1362,15 +1302,8 @@ static stark_status ntt_device_plan(stark_ctx* ctx, const fe* src, uint32_t zero
     }
     const int col = (log_ns == 0 || fused_in) ? (sp.skip ? kColSparse : kColNone)
                     : full ? kColFull : log_ns + lr <= tw.l16 ? kColT16 : kColTwoLevel;
-    // data image + staged Shoup pairs + digit-basis tables (DbPlan of this instance)
-    const size_t image = std::max((size_t)elems, db_full_fe(lr, col));
-    const size_t lds = (image + db_lds_fe(lr, col)) * sizeof(fe);
-    const pass_fn fn = pass_kernel(lr, col, fuse);
-    if (!fn) return STARK_ERR_BAD_ARG;  // (fuse_modes selects only instances that exist)
-    hipLaunchKernelGGL(fn, dim3((unsigned)total), dim3(threads), lds, stream, cur, dst, log_n,
-                       log_ns, lb, ct, tw.d_small + tw.small_off[lr], tw.d_db + tw.db_off[lr], scale,
-                       (inverse && last && !fold && !fused_in) ? 1 : 0, log_tiles, (uint32_t)total, sp);
-    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(launch_pass(ctx, stream, tw, cur, dst, log_n, log_ns, lr, batch, col, fuse, ct,
+                          (inverse && last && !fold && !fused_in) ? 1 : 0, sp));
     cur = dst;
     log_ns += lr;
   }
@@ -1387,22 +1320,9 @@ stark_status ntt_first_pass_tmajor(stark_ctx* ctx, const fe* src, uint32_t zero_
   if (((uint64_t)batch << log_n) > ((uint64_t)1 << 34)) return STARK_ERR_BAD_ARG;
   const uint32_t lr = plan_passes(log_n).log_r[0];
   if (zero_log > lr) return STARK_ERR_BAD_ARG;  // (the LDEs here: zero_log 3 <= every plan's first radix)
-  uint32_t k = zero_log;
-  if ((k & 1) != (lr & 1)) --k;
-  const Sparse sp{k, zero_log, log_n - zero_log};
-  const uint32_t lb = choose_log_b_impl(log_n, lr, kTileLog);
-  const uint32_t elems = 1u << (lr + lb);
-  const uint32_t threads = elems / 4 < 64 ? 64 : elems / 4;
-  const uint32_t log_tiles = log_n - lr - lb;
-  const uint64_t total = (uint64_t)batch << log_tiles;
-  const int col = sp.skip ? kColSparse : kColNone;
-  const ColTw ct{tw.d_t16, tw.d_lo, tw.d_hi, nullptr, tw.l16, tw.kb, nullptr};
-  const size_t image = std::max((size_t)elems, db_full_fe(lr, col));
-  const size_t lds = (image + db_lds_fe(lr, col)) * sizeof(fe);
-  hipLaunchKernelGGL(pass_kernel(lr, col), dim3((unsigned)total), dim3(threads), lds, stream, src, out, log_n,
-                     log_n - lr, lb, ct, tw.d_small + tw.small_off[lr], tw.d_db + tw.db_off[lr], to_dev(tw.inv_n), 0,
-                     log_tiles, (uint32_t)total, sp);
-  STARK_HIP(ctx, hipGetLastError());
+  const Sparse sp = sparse_first(zero_log, lr, log_n);
+  STARK_TRY(launch_pass(ctx, stream, tw, src, out, log_n, log_n - lr, lr, batch, sp.skip ? kColSparse : kColNone,
+                        kFuseNone, col_tw(tw, false), 0, sp));
   *log_t = lr;
   return STARK_OK;
 }

@@ -1,0 +1,111 @@
+"""GPU parity of every unfused ntt_pass_kernel instance (csrc/ntt.hip): radices 2^2..2^9, each with no
+column twiddle, Shoup pairs from t16, the last pass's full table, and the two-level lo * hi form.
+
+The default plans launch only some of these; the rest are reached through the library's test hook
+`stark_test_ntt_plan` with policy 3 (no fusion).  For each radix r:
+  * (4, r) and (r, 4) at 2^(4 + r): r as a last pass on t16 and as a first pass, with partial tiles
+    (the radix-2^9 first pass also takes the store's Ns < B path);
+  * prefix + (r,) at 2^17, once on the shared context, where the last pass takes the cached full
+    table, and once on a context whose cache cap is 0, where it takes the two-level form.
+Forward and inverse are compared bit for bit with the oracle; the 2^17 plans share one expected output
+per direction.
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import oracle as O
+import stark_amd as S
+
+pytestmark = pytest.mark.gpu
+
+OFF = 3  # the hook's fusion policy: none
+RADICES = range(2, 10)
+PREFIX_2_17 = {2: (8, 7), 3: (7, 7), 4: (7, 6), 5: (6, 6), 6: (6, 5), 7: (5, 5), 8: (9,), 9: (8,)}
+
+
+def _hook():
+    fn = S.load_library().stark_test_ntt_plan
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                   ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
+                   ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+    fn.restype = ctypes.c_int
+    return fn
+
+
+def _limbs(x):
+    return (ctypes.c_uint64 * 4)(*[(x >> (64 * k)) & (2**64 - 1) for k in range(4)])
+
+
+def _plan_ntt(c, log_n, inverse, plan):
+    assert sum(plan) == log_n
+    x = _input(log_n)
+    used = ctypes.c_uint32(0xFFFFFFFF)
+    d = c.alloc(x.nbytes)
+    try:
+        c.h2d(d, np.array(x))
+        radices = (ctypes.c_uint32 * len(plan))(*plan)
+        rc = _hook()(c.h, d, log_n, 1, _limbs(O.root_of_unity(log_n)), int(inverse), radices, len(plan), OFF, None,
+                     ctypes.byref(used))
+        assert rc == 0, rc
+        out = np.empty_like(x)
+        c.d2h(out, d)
+    finally:
+        c.free(d)
+    assert used.value == 0
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _input(log_n):
+    x = O.random_elements(1 << log_n, 0x1A57A9CE + log_n)
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def _want(log_n, inverse):
+    """The oracle's transform of _input(log_n), computed once."""
+    o = O.Oracle()
+    f = o.inv_best_fft if inverse else o.best_fft
+    out = f(np.array(_input(log_n)), O.root_of_unity(log_n), log_n, cpus=8)
+    out.setflags(write=False)
+    return out
+
+
+@pytest.fixture(scope="module")
+def ctx_nocache():
+    c = S.Context(0)
+    c.set_cache_limit(0)
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("first", [False, True], ids=["last", "first"])
+@pytest.mark.parametrize("r", RADICES)
+def test_small_pair(ctx, r, first):
+    log_n = 4 + r
+    plan = (r, 4) if first else (4, r)
+    for inverse in (False, True):
+        got = _plan_ntt(ctx, log_n, inverse, plan)
+        assert np.array_equal(got, _want(log_n, inverse)), (plan, inverse)
+
+
+@pytest.mark.parametrize("r", RADICES)
+def test_2_17_full_table(ctx, r):
+    plan = PREFIX_2_17[r] + (r,)
+    for inverse in (False, True):
+        got = _plan_ntt(ctx, 17, inverse, plan)
+        assert np.array_equal(got, _want(17, inverse)), (plan, inverse)
+    assert ctx.memory()["cached"] >= 2 * (32 << 17)  # (both directions' last passes read a cached table)
+
+
+@pytest.mark.parametrize("r", RADICES)
+def test_2_17_two_level(ctx_nocache, r):
+    plan = PREFIX_2_17[r] + (r,)
+    for inverse in (False, True):
+        got = _plan_ntt(ctx_nocache, 17, inverse, plan)
+        assert np.array_equal(got, _want(17, inverse)), (plan, inverse)
+    assert ctx_nocache.memory()["cached"] == 0

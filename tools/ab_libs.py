@@ -5,7 +5,8 @@ Each build is loaded with its own ctypes handle and context; the timed loops alt
 builds in rounds so that clock and thermal drift hit every build alike.  For each build and case it
 prints the median ms per call and a digest of the output, which must agree across builds.
 
-usage: python tools/ab_libs.py [--cases ntt20,ntt24,ntt26,intt24,lde20] [--reps 30] [--rounds 5] lib.so ...
+usage: python tools/ab_libs.py [--cases ntt20,ntt24,ntt26,intt24] [--reps 30] [--rounds 5] lib.so ...
+(the LDE, whose first pass is sparse, is timed by tools/time_lde.py)
 """
 import argparse
 import ctypes

@@ -6,8 +6,8 @@ def apply(s):
         for (int t = 0; t < 4; ++t) tw[t] = fe_load_nt(ct.full + ((((j0 + eb[t]) & ns_mask) << LOG_R) + er[t]));
         // Montgomery images (the table streams from HBM once per transform, so it stays 32 B per
         // entry): v < 4p, tw < p -> [0, 2p); two interleaved products per block
-        mul2(v[0], v[1], v[0], tw[0], v[1], tw[1]);
-        mul2(v[2], v[3], v[2], tw[2], v[3], tw[3]);''',
+        fe_mul_lazy2(v[0], v[1], v[0], tw[0], v[1], tw[1]);
+        fe_mul_lazy2(v[2], v[3], v[2], tw[2], v[3], tw[3]);''',
          '''        fe twq[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -15,8 +15,8 @@ def apply(s):
           tw[t] = fe_load_nt(e);
           twq[t] = fe_load_nt(e + 1);
         }
-        shoup2(v[0], v[1], v[0], tw[0], twq[0], v[1], tw[1], twq[1]);
-        shoup2(v[2], v[3], v[2], tw[2], twq[2], v[3], tw[3], twq[3]);'''),
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = fe_mul_shoup(v[t], tw[t], twq[t]);'''),
         ('''  fe t = fe_mul(lo[e & (((uint64_t)1 << kb) - 1)], hi[e >> kb]);
   if (do_scale) t = fe_mul(t, scale);
   fe_store(out + g, t);''',

@@ -4,9 +4,13 @@
 # usage: OCC=all|last tools/build_variant.sh ab/occ.so @tools/ntt_variants/e5_2_20_two_wg.py
 import os
 def apply(s):
-    old = "    const size_t lds = (image + db_lds_fe(lr, col)) * sizeof(fe);\n"
+    # launch_pass serves the transform's passes and ntt_first_pass_tmajor; only the former are meant.  2^20's plan
+    # fuses nothing, so a pass with Ns > 1 and no column twiddle is the t-major first pass.
+    old = "  const size_t lds = (image + pi.extra_fe) * sizeof(fe);\n"
     assert s.count(old) == 1
-    cond = "log_n == 20" + (" && last" if os.environ["OCC"] == "last" else "")
-    new = ("    size_t lds = (image + db_lds_fe(lr, col)) * sizeof(fe);\n"
-           f"    if ({cond} && lds < 56 * 1024) lds = 56 * 1024;\n")
+    cond = "log_n == 20 && !(log_ns > 0 && (col == kColNone || col == kColSparse))"
+    if os.environ["OCC"] == "last":
+        cond += " && log_ns + lr == log_n"
+    new = ("  size_t lds = (image + pi.extra_fe) * sizeof(fe);\n"
+           f"  if ({cond} && lds < 56 * 1024) lds = 56 * 1024;\n")
     return s.replace(old, new)
