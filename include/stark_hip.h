@@ -35,8 +35,9 @@ extern "C" {
 #endif
 
 /* 2: stark_r1cs_proof_branches takes leaves_cap / nodes_cap (round 4).
- * 3: device groups, stark_group_* (round 6). */
-#define STARK_ABI_VERSION 3u
+ * 3: device groups, stark_group_* (round 6).
+ * 4: stark_group_prove_low_degree(_dev), stark_class_deal_dev / stark_class_merge_dev. */
+#define STARK_ABI_VERSION 4u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -342,6 +343,18 @@ stark_status stark_ntt_strided_tw_dev(stark_ctx* ctx, uint64_t* d_data, uint32_t
                                       const uint64_t root[4], int inverse, const uint64_t tw_root[4],
                                       uint32_t log_order, uint64_t tw_base, void* stream);
 
+/* A contiguous block of n_block elements dealt into `world` (1, 2, 4 or 8) residue-class chunks of
+ * n_block / world elements, chunk r at d_chunks + 4 r n_block / world u64: chunk r, element j is
+ * d_block[r + world j]; and its inverse.  What a member of a group does to its block of a host vector
+ * before the all-to-all that leaves member r holding class r, and how class chunks gathered on one member
+ * become a vector in natural order.  Asynchronous on `stream`.  STARK_ERR_BAD_ARG for another world, for
+ * buffers that overlap or are not 16-B aligned; STARK_ERR_BAD_LENGTH when world does not divide n_block;
+ * n_block = 0 is a no-op. */
+stark_status stark_class_deal_dev(stark_ctx* ctx, const uint64_t* d_block, uint64_t* d_chunks, size_t n_block,
+                                  uint32_t world, void* stream);
+stark_status stark_class_merge_dev(stark_ctx* ctx, const uint64_t* d_chunks, uint64_t* d_block, size_t n_block,
+                                   uint32_t world, void* stream);
+
 /* ---- distributed Merkle / FRI / prover building blocks ---------------------
  * (no reference counterpart: the reference prover is single-process; these let
  * `world` GPUs share one proof, see stark-pure-rust_amd/stark_amd/dprove.py.)
@@ -491,6 +504,20 @@ size_t stark_group_merkle_width(const stark_group_tree* tree);
 stark_status stark_group_merkle_get_root(const stark_group_tree* tree, uint8_t root[32], size_t* root_len);
 stark_status stark_group_merkle_gen_proofs(stark_group_tree* tree, const size_t* indices, size_t k,
                                            uint8_t* leaves_out, uint8_t* nodes_out);
+/* fri::prove_low_degree (fri.rs:46-62) over the group; same arguments, statuses and result type as
+ * stark_prove_low_degree: the stark_fri_proof works with stark_fri_proof_{json,num_layers,layer_info,layer_data,free}.
+ * With G > 1, n > 2^16 and max_deg_plus_1 > 16 the layers are folded by residue class on the members while
+ * they hold more than 2^16 values (each tree one digest all-to-all), and member 0 proves the rest from a
+ * device hand-off; anything smaller is stark_prove_low_degree on member 0.  Member b uploads its block
+ * values[b n/G, (b+1) n/G) straight from the caller's memory. */
+stark_status stark_group_prove_low_degree(stark_group* group, const uint64_t* values, size_t n, const uint64_t root[4],
+                                          size_t max_deg_plus_1, uint32_t exclude_multiples_of,
+                                          stark_fri_proof** out);
+/* Values already on the members: d_class[r] (member r's device) holds values[r + G j], j < n/G; not modified.
+ * n must be a multiple of G (STARK_ERR_BAD_LENGTH). */
+stark_status stark_group_prove_low_degree_dev(stark_group* group, const uint64_t* const* d_class, size_t n,
+                                              const uint64_t root[4], size_t max_deg_plus_1,
+                                              uint32_t exclude_multiples_of, stark_fri_proof** out);
 /* prove_with_witness (run.rs:310-452) with one proof shared by the group: member r owns
  * the precision-domain points r + G j; coset LDEs, constraints and FRI folds are local, each Merkle tree
  * is one digest all-to-all; the proof equals stark_prove_r1cs_bytes' byte for byte. */

@@ -2,6 +2,7 @@
 // a tiled transpose of 32-B field elements and the four-step twiddle
 // data[i][j] *= w^((row_base + i) * (col_base + j)).  The exchange steps are
 // RCCL all-to-alls issued by the caller (torch.distributed, backend "nccl").
+// Also the residue-class deal / merge of a device group's FRI (group.hip).
 #include "fe_db.h"
 #include "internal.h"
 
@@ -128,11 +129,68 @@ __global__ __launch_bounds__(256) void strided_ntt_kernel(fe* __restrict__ d, ui
   for (int k = 0; k < G; ++k) fe_store(d + i + stride * (uint64_t)k, do_scale ? fe_mul(x[k], scale) : x[k]);
 }
 
+// A contiguous block of n field elements dealt into its 2^log_w residue classes and back (the group FRI's
+// way in and its hand-off to the tail, group.hip): chunk r, element j is block[r + 2^log_w j].  A
+// (n / world) x world transpose of 32-B elements with no arithmetic, so one 16-B half per lane: the lanes
+// run along the block, whose side is whole 1-KB wave runs, and a wave's 32 elements fall into world runs
+// of 1024 / world B on the class side (128 B at world = 8: whole 32-B sectors, no partial store).
+__device__ __forceinline__ uint64_t class_half_at(uint64_t t, uint64_t m, uint32_t log_w) {
+  const uint64_t e = t >> 1, r = e & (((uint64_t)1 << log_w) - 1), j = e >> log_w;
+  return 2 * (r * m + j) + (t & 1);
+}
+
+// halves = 2 n; m = n / world
+__global__ __launch_bounds__(256) void class_deal_kernel(const uint4* __restrict__ block, uint4* __restrict__ chunks,
+                                                         uint64_t halves, uint64_t m, uint32_t log_w) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < halves) chunks[class_half_at(t, m, log_w)] = block[t];
+}
+
+__global__ __launch_bounds__(256) void class_merge_kernel(const uint4* __restrict__ chunks, uint4* __restrict__ block,
+                                                          uint64_t halves, uint64_t m, uint32_t log_w) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < halves) block[t] = chunks[class_half_at(t, m, log_w)];
+}
+
+static stark_status class_move(stark_ctx* ctx, const uint64_t* d_in, uint64_t* d_out, size_t n_block, uint32_t world,
+                               bool merge, void* stream) {
+  if (!ctx || !d_in || !d_out) return STARK_ERR_BAD_ARG;
+  if (world != 1 && world != 2 && world != 4 && world != 8) return STARK_ERR_BAD_ARG;
+  if (n_block % world != 0 || n_block > ((size_t)1 << 36)) return STARK_ERR_BAD_LENGTH;  // (a grid of 2^29 blocks)
+  const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out, bytes = n_block * sizeof(fe);
+  if (((a | b) & 15) || (a < b + bytes && b < a + bytes) || a == b) return STARK_ERR_BAD_ARG;
+  if (n_block == 0) return STARK_OK;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  uint32_t log_w = 0;
+  while ((1u << log_w) < world) ++log_w;
+  const uint64_t halves = 2 * (uint64_t)n_block;
+  const dim3 grid((unsigned)((halves + 255) / 256));
+  hipStream_t s = pick_stream(ctx, stream);
+  if (merge)
+    hipLaunchKernelGGL(class_merge_kernel, grid, dim3(256), 0, s, (const uint4*)d_in, (uint4*)d_out, halves,
+                       (uint64_t)(n_block / world), log_w);
+  else
+    hipLaunchKernelGGL(class_deal_kernel, grid, dim3(256), 0, s, (const uint4*)d_in, (uint4*)d_out, halves,
+                       (uint64_t)(n_block / world), log_w);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
 }  // namespace stark
 
 using namespace stark;
 
 extern "C" {
+
+stark_status stark_class_deal_dev(stark_ctx* ctx, const uint64_t* d_block, uint64_t* d_chunks, size_t n_block,
+                                  uint32_t world, void* stream) {
+  return class_move(ctx, d_block, d_chunks, n_block, world, false, stream);
+}
+
+stark_status stark_class_merge_dev(stark_ctx* ctx, const uint64_t* d_chunks, uint64_t* d_block, size_t n_block,
+                                   uint32_t world, void* stream) {
+  return class_move(ctx, d_chunks, d_block, n_block, world, true, stream);
+}
 
 stark_status stark_transpose_dev(stark_ctx* ctx, const uint64_t* d_src, uint64_t* d_dst, size_t rows, size_t cols,
                                  uint32_t batch, void* stream) {

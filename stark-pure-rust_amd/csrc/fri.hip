@@ -162,20 +162,14 @@ struct FriPending {
   const uint8_t* h_roots = nullptr;  // pinned: roots of trees[0..layers]
 };
 
-// prove_low_degree on device values, phase 1.  Per layer everything is
-// enqueued on the context stream with no host round trip: build the values'
-// tree, derive special_x from its root on the device, fold, build the
-// column's tree; finally the roots are queued for download.
 void FriPendingDeleter::operator()(FriPending* p) const { delete p; }
 
-stark_status fri_enqueue(stark_ctx* ctx, const fe* d_values, size_t n, const uint64_t root[4], size_t max_deg_plus_1,
-                         uint32_t excl, FriPendingPtr* out, stark_merkle_tree* tree0, bool sx0_made) {
+// prove_low_degree's argument checks (the reference panics on these), shared with the group entry points
+// so that they return the same status: the layer sizes, the index sampler's modulus, and n = the order
+// of root where a layer is folded (whose inverse-root tables are *tw_out).
+stark_status fri_check(stark_ctx* ctx, size_t n, const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,
+                       size_t* n_layers, const Twiddles** tw_out) {
   const FieldHost& F = FieldHost::get();
-  hipStream_t s = ctx->stream;
-  FriPendingPtr p(new FriPending());
-  p->proof = std::make_unique<stark_fri_proof>();
-  p->excl = excl;
-  // Layer sizes and checks up front (the reference panics on these).
   size_t layers = 0;
   {
     size_t m = n, deg = max_deg_plus_1;
@@ -189,17 +183,36 @@ stark_status fri_enqueue(stark_ctx* ctx, const fe* d_values, size_t n, const uin
     }
   }
   if (layers + 1 > 16) return STARK_ERR_BAD_LENGTH;
-  p->layers = layers;
   const Twiddles* tw = nullptr;
-  uint32_t log_n0 = 0;
-  while (((size_t)1 << log_n0) < n) ++log_n0;
   if (layers > 0) {
     // values.len() must equal the order of root (xs = expand_root_of_unity, fri.rs:84).
+    uint32_t log_n0 = 0;
+    while (((size_t)1 << log_n0) < n) ++log_n0;
     uint64_t inv_root[4];
     F.to_canonical(F.inv(F.from_canonical(root)), inv_root);
-    stark_status st = get_twiddles(ctx, inv_root, log_n0, &tw);
-    if (st != STARK_OK) return st;
+    STARK_TRY(get_twiddles(ctx, inv_root, log_n0, &tw));
   }
+  if (n_layers) *n_layers = layers;
+  if (tw_out) *tw_out = tw;
+  return STARK_OK;
+}
+
+// prove_low_degree on device values, phase 1.  Per layer everything is
+// enqueued on the context stream with no host round trip: build the values'
+// tree, derive special_x from its root on the device, fold, build the
+// column's tree; finally the roots are queued for download.
+stark_status fri_enqueue(stark_ctx* ctx, const fe* d_values, size_t n, const uint64_t root[4], size_t max_deg_plus_1,
+                         uint32_t excl, FriPendingPtr* out, stark_merkle_tree* tree0, bool sx0_made) {
+  const FieldHost& F = FieldHost::get();
+  hipStream_t s = ctx->stream;
+  FriPendingPtr p(new FriPending());
+  p->proof = std::make_unique<stark_fri_proof>();
+  p->excl = excl;
+  // Layer sizes and checks up front (the reference panics on these).
+  size_t layers = 0;
+  const Twiddles* tw = nullptr;
+  STARK_TRY(fri_check(ctx, n, root, max_deg_plus_1, excl, &layers, &tw));
+  p->layers = layers;
   // Column buffers: n/4 + n/16 + ... elements; special_x per layer; the roots.
   size_t col_total = 0;
   {
@@ -629,44 +642,18 @@ void fri_proof_json_string(const stark_fri_proof* proof, std::string& o) {
   j.render(o);
 }
 
-}  // namespace stark
-
-using namespace stark;
-
-extern "C" {
-
-stark_status stark_prove_low_degree_dev(stark_ctx* ctx, const uint64_t* d_values, size_t n, const uint64_t root[4],
-                                        size_t max_deg_plus_1, uint32_t exclude_multiples_of, stark_fri_proof** out) {
-  if (!ctx || !root || !out || (n && !d_values)) return STARK_ERR_BAD_ARG;
-  *out = nullptr;
-  STARK_HIP(ctx, hipSetDevice(ctx->device));
-  return fri_prove_device(ctx, (const fe*)d_values, n, root, max_deg_plus_1, exclude_multiples_of, out);
-}
-
-stark_status stark_prove_low_degree(stark_ctx* ctx, const uint64_t* values, size_t n, const uint64_t root[4],
-                                    size_t max_deg_plus_1, uint32_t exclude_multiples_of, stark_fri_proof** out) {
-  if (!ctx || !root || !out || (n && !values)) return STARK_ERR_BAD_ARG;
-  *out = nullptr;
-  STARK_HIP(ctx, hipSetDevice(ctx->device));
-  stark_status st = ensure_buf(ctx, ctx->io, (n ? n : 1) * sizeof(fe));
-  if (st != STARK_OK) return st;
-  if (n) STARK_HIP(ctx, hipMemcpyAsync(ctx->io.ptr, values, n * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
-  st = fri_prove_device(ctx, (const fe*)ctx->io.ptr, n, root, max_deg_plus_1, exclude_multiples_of, out);
-  hipStreamSynchronize(ctx->stream);
-  return st;
-}
-
-void stark_fri_proof_free(stark_fri_proof* proof) { delete proof; }
-
 // One FRI fold on this GPU's residue class (distributed prover, fri.rs:135-164):
 // `values` holds the layer's values at the points rank + world*j (n/world of
 // them), `column` receives the folded column at the same residue class of the
 // n/4 rows; special_x = from_bytes_le(m_root) (fri.rs:135).
 // special_x from a host root (m_root) or a device-resident one (d_m_root: the fold reads it on the stream,
 // no host round trip).
-static stark_status fri_fold(stark_ctx* ctx, const uint64_t* values, uint64_t* column, size_t n,
-                             const uint64_t root[4], const uint8_t* m_root, const uint8_t* d_m_root, uint32_t world,
-                             uint32_t rank, void* stream) {
+// d_digests non-null: the Blake2s of each folded value too (n / (4 world) x 32 B, 16-B aligned): the leaf
+// digests of the column's tree from the same launch.
+stark_status fri_fold(stark_ctx* ctx, const uint64_t* values, uint64_t* column, size_t n, const uint64_t root[4],
+                      const uint8_t* m_root, const uint8_t* d_m_root, uint32_t world, uint32_t rank,
+                      uint8_t* d_digests, void* stream) {
+  if (((uintptr_t)d_digests) & 15) return STARK_ERR_BAD_ARG;
   if (!ctx || !values || !column || !root || (!m_root && !d_m_root)) return STARK_ERR_BAD_ARG;
   if (world == 0 || (world & (world - 1)) || rank >= world) return STARK_ERR_BAD_ARG;
   if (n < 4 || (n & (n - 1)) || (n / 4) % world != 0) return STARK_ERR_BAD_LENGTH;
@@ -698,25 +685,54 @@ static stark_status fri_fold(stark_ctx* ctx, const uint64_t* values, uint64_t* c
   const size_t q = n / 4 / world;
   hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, s, (const fe*)values,
                      (fe*)column, (uint64_t)q, (uint32_t)0, (uint64_t)rank, log_g, tw->d_lo, tw->d_hi, tw->kb,
-                     (const fe*)d_sx, to_dev(zeta), to_dev(F.inv(F.from_u64(4))), (uint32_t*)nullptr);
+                     (const fe*)d_sx, to_dev(zeta), to_dev(F.inv(F.from_u64(4))), (uint32_t*)d_digests);
   STARK_HIP(ctx, hipGetLastError());
   STARK_TRY(buf_release(ctx, ctx->fri_misc, s));
   if (m_root) STARK_HIP(ctx, hipStreamSynchronize(s));  // sx lives on this stack frame
   return STARK_OK;
 }
 
+}  // namespace stark
+
+using namespace stark;
+
+extern "C" {
+
+stark_status stark_prove_low_degree_dev(stark_ctx* ctx, const uint64_t* d_values, size_t n, const uint64_t root[4],
+                                        size_t max_deg_plus_1, uint32_t exclude_multiples_of, stark_fri_proof** out) {
+  if (!ctx || !root || !out || (n && !d_values)) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  return fri_prove_device(ctx, (const fe*)d_values, n, root, max_deg_plus_1, exclude_multiples_of, out);
+}
+
+stark_status stark_prove_low_degree(stark_ctx* ctx, const uint64_t* values, size_t n, const uint64_t root[4],
+                                    size_t max_deg_plus_1, uint32_t exclude_multiples_of, stark_fri_proof** out) {
+  if (!ctx || !root || !out || (n && !values)) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  stark_status st = ensure_buf(ctx, ctx->io, (n ? n : 1) * sizeof(fe));
+  if (st != STARK_OK) return st;
+  if (n) STARK_HIP(ctx, hipMemcpyAsync(ctx->io.ptr, values, n * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
+  st = fri_prove_device(ctx, (const fe*)ctx->io.ptr, n, root, max_deg_plus_1, exclude_multiples_of, out);
+  hipStreamSynchronize(ctx->stream);
+  return st;
+}
+
+void stark_fri_proof_free(stark_fri_proof* proof) { delete proof; }
+
 stark_status stark_fri_fold_dev(stark_ctx* ctx, const uint64_t* values, uint64_t* column, size_t n,
                                 const uint64_t root[4], const uint8_t m_root[32], uint32_t world, uint32_t rank,
                                 void* stream) {
   if (!m_root) return STARK_ERR_BAD_ARG;
-  return fri_fold(ctx, values, column, n, root, m_root, nullptr, world, rank, stream);
+  return fri_fold(ctx, values, column, n, root, m_root, nullptr, world, rank, nullptr, stream);
 }
 
 stark_status stark_fri_fold_dev_root(stark_ctx* ctx, const uint64_t* values, uint64_t* column, size_t n,
                                      const uint64_t root[4], const uint8_t* d_m_root, uint32_t world, uint32_t rank,
                                      void* stream) {
   if (!d_m_root || (((uintptr_t)d_m_root) & 3)) return STARK_ERR_BAD_ARG;
-  return fri_fold(ctx, values, column, n, root, nullptr, d_m_root, world, rank, stream);
+  return fri_fold(ctx, values, column, n, root, nullptr, d_m_root, world, rank, nullptr, stream);
 }
 
 // serde_json of a StarkProof (r1cs-stark/src/utils.rs:122-130) from its parts

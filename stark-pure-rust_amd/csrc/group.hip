@@ -2,8 +2,8 @@
 // ctx group created once"; 8(e)).  The reference's only parallelism is the thread pool a call builds
 // for itself (Worker::new inside best_fft, fri/src/fft.rs:332; commitment/src/multicore.rs:43-45); a
 // group is that pool with GPUs as its workers, created once by the caller and handed to the group
-// entry points, which keep the reference's signatures (best_fft / inv_best_fft, MerkleTree, and
-// prove_with_witness).
+// entry points, which keep the reference's signatures (best_fft / inv_best_fft, MerkleTree,
+// prove_low_degree and prove_with_witness).
 //
 // Transport: peer copies.  Every exchange is pulled by the receiving member on its own stream, after an
 // event wait on each sender's stream (hipMemcpyPeerAsync between devices over xGMI, a device-to-device
@@ -19,6 +19,8 @@
 //  - Merkle: contiguous leaf blocks per member, subtree roots gathered to member 0, the top log2 G
 //    levels hashed there -- the reference's own subtree + top-tree split
 //    (commitment/src/merkle_proof_in_place.rs:106-206);
+//  - FRI: class-local folds that hash their outputs, one digest all-to-all per tree, the tail on member 0
+//    from a device hand-off (gather + class merge); one implementation for the entry point and the prover;
 //  - prover: the residue-class layout of stark_amd/dprove.py: coset LDEs, constraints
 //    and FRI folds local, Merkle trees by one digest all-to-all each.
 #include <string.h>
@@ -424,29 +426,11 @@ stark_status tree_prepare(stark_group_tree* t, size_t n, size_t leaf_len) {
 }
 
 // ---- prover --------------------------------------------------------------------------------------
-// A Merkle tree over n leaves held by residue class (member r: leaves r + G j), stark_amd/dprove.py
-// DistTree: digests hashed where the leaves are, one all-to-all of digests, member s builds the subtree of
-// leaves [s P, (s+1) P), the subtree roots gathered to every member, and the top levels hashed on each
-// (every member's next step reads the root on its own stream).
-struct DTree {
-  bool blocked = false;
-  size_t n = 0, nl = 0, leaf_len = 0;
-  std::vector<const uint8_t*> leaves;
-  std::vector<stark_merkle_tree*> t;
-  std::vector<uint8_t*> levels;  // blocked: G roots then the G - 1 above (root last); else the root
-  std::vector<uint8_t> host;
-  const uint8_t* d_root(size_t r, size_t G) const { return levels[r] + (blocked ? (2 * G - 2) * 32 : 0); }
-  const uint8_t* root() const { return host.data() + host.size() - 32; }
-  size_t level_width(size_t G, uint32_t lvl) const { return G >> lvl; }
-  const uint8_t* level_node(size_t G, uint32_t lvl, size_t i) const {
-    size_t at = 0;
-    for (uint32_t l = 0; l < lvl; ++l) at += G >> l;
-    return host.data() + 32 * (at + i);
-  }
-};
+}  // namespace
 
-stark_status dtree_commit(stark_group* g, DTree& d, const std::vector<const uint8_t*>& leaves, size_t nl,
-                          size_t leaf_len) {
+// The DTree of internal.h from its leaves' digests (dig[r]: member r's nl digests).
+stark_status dtree_commit_digests(stark_group* g, DTree& d, const std::vector<const uint8_t*>& leaves, size_t nl,
+                                  size_t leaf_len, const std::vector<uint8_t*>& dig) {
   const size_t G = g->m.size();
   d.leaves = leaves;
   d.nl = nl;
@@ -455,17 +439,14 @@ stark_status dtree_commit(stark_group* g, DTree& d, const std::vector<const uint
   d.blocked = nl % G == 0;
   d.t.assign(G, nullptr);
   d.levels.assign(G, nullptr);
-  std::vector<uint8_t*> dig(G), recv(G), mine(G);
+  std::vector<uint8_t*> recv(G);
   for (size_t r = 0; r < G; ++r) {
     void* p;
-    STARK_TRY(take(g, r, nl * 32, &p));
-    dig[r] = (uint8_t*)p;
     STARK_TRY(take(g, r, d.blocked ? nl * 32 : d.n * 32, &p));
     recv[r] = (uint8_t*)p;
     STARK_TRY(take(g, r, (2 * G - 1) * 32, &p));
     d.levels[r] = (uint8_t*)p;
     STARK_TRY(take_tree(g, r, &d.t[r]));
-    STARK_TRY(gfail(g, r, stark_merkle_leaf_digests_dev(g->m[r], leaves[r], nl, leaf_len, dig[r], nullptr)));
   }
   std::vector<const uint8_t*> send(dig.begin(), dig.end());
   if (!d.blocked) {
@@ -486,6 +467,21 @@ stark_status dtree_commit(stark_group* g, DTree& d, const std::vector<const uint
     STARK_TRY(gfail(g, r, stark_merkle_top_dev(g->m[r], d.levels[r], G, d.levels[r] + 32 * G, nullptr)));
   return STARK_OK;
 }
+
+stark_status dtree_commit(stark_group* g, DTree& d, const std::vector<const uint8_t*>& leaves, size_t nl,
+                          size_t leaf_len) {
+  const size_t G = g->m.size();
+  std::vector<uint8_t*> dig(G);
+  for (size_t r = 0; r < G; ++r) {
+    void* p;
+    STARK_TRY(take(g, r, nl * 32, &p));
+    dig[r] = (uint8_t*)p;
+    STARK_TRY(gfail(g, r, stark_merkle_leaf_digests_dev(g->m[r], leaves[r], nl, leaf_len, dig[r], nullptr)));
+  }
+  return dtree_commit_digests(g, d, leaves, nl, leaf_len, dig);
+}
+
+namespace {
 
 // Openings of `idx` from a DTree: member (i mod G) holds leaf i, member (i / P) its lower path (member 0
 // the whole path of an unblocked tree), the top levels come from the downloaded roots.
@@ -568,12 +564,227 @@ stark_status indices(const uint8_t* seed, size_t modulus, size_t count, uint32_t
   return STARK_OK;
 }
 
+// Every member gathers what it holds of the openings in one zero-copy launch; then they are assembled.
+stark_status open_all(stark_group* g, std::vector<DOpen>& opens) {
+  const size_t G = g->m.size();
+  STARK_TRY(for_members(g, [&](size_t r) {
+    std::vector<stark_open_req> reqs;
+    for (DOpen& o : opens) {
+      const DTree& d = *o.d;
+      stark_open_req a{};
+      a.d_rows = d.leaves[r];
+      a.row_bytes = d.leaf_len;
+      a.n_rows = d.nl;
+      a.idx = o.leaf_local[r].data();
+      a.k = o.leaf_local[r].size();
+      a.leaves_out = o.leaf_out[r].data();
+      reqs.push_back(a);
+      stark_open_req b{};
+      b.tree = d.t[r];
+      b.idx = o.path_local[r].data();
+      b.k = o.path_local[r].size();
+      b.nodes_out = o.path_out[r].data();
+      reqs.push_back(b);
+    }
+    return stark_open_batch(g->m[r], reqs.data(), reqs.size(), nullptr);
+  }));
+  for (DOpen& o : opens) dopen_assemble(o, G);
+  return STARK_OK;
+}
+
+// ---- FRI -----------------------------------------------------------------------------------------
+// prove_low_degree (fri.rs:46-224) over class-distributed values, for the prover's L and for the group's
+// own entry points.  The layers are folded where the values are while they are large (deg > 16 and more
+// than 2^kFriTailLog values); what is left is either the Last layer (deg <= 16: the values are the proof
+// and come to the host) or member 0's: the class chunks gathered there, merged into natural order on the
+// device, and proved by stark_prove_low_degree_dev.  Four steps, so that a caller with trees and openings
+// of its own (group_prove) still downloads the roots once and opens once per member:
+//   gfri_commit (enqueue) -> gfri_download (the one synchronisation) -> gfri_plan + open_all -> gfri_finish.
+struct GroupFri {
+  struct Layer {
+    DTree t2;         // the folded column's tree
+    const DTree* mt;  // the tree of the values it was folded from
+    size_t q;
+  };
+  std::vector<std::unique_ptr<Layer>> layers;
+  std::vector<const uint8_t*> vals;  // the last distributed column, per member
+  size_t n = 0, deg = 0;             // its length and degree bound
+  uint32_t excl = 0;
+  uint64_t wc[4] = {0, 0, 0, 0};     // its root of unity
+  const uint64_t* d_tail = nullptr;  // deg > 16: the column in natural order on member 0
+  std::vector<uint8_t> last_local;   // deg <= 16: the classes on the host, member order
+};
+
+// vals[r]: member r's class of the n values (device), committed in *mtree; root of order n.
+stark_status gfri_commit(stark_group* g, const std::vector<const uint8_t*>& vals, const DTree* mtree, size_t n,
+                         const uint64_t root[4], size_t deg, uint32_t excl, GroupFri& f) {
+  const size_t G = g->m.size();
+  const FieldHost& F = FieldHost::get();
+  f.vals = vals;
+  f.excl = excl;
+  HostFp w = F.from_canonical(root);
+  // the fold's special_x comes from the previous tree's root on the device; the fold hashes its outputs,
+  // which are the next tree's leaves
+  while (deg > 16 && n > ((size_t)1 << kFriTailLog)) {
+    const size_t q = n / 4;
+    uint64_t wc[4];
+    canon(w, wc);
+    std::vector<const uint8_t*> col(G);
+    std::vector<uint8_t*> dig(G);
+    for (size_t r = 0; r < G; ++r) {
+      void *p, *d;
+      STARK_TRY(take(g, r, q / G * 32, &p));
+      STARK_TRY(take(g, r, q / G * 32, &d));
+      col[r] = (const uint8_t*)p;
+      dig[r] = (uint8_t*)d;
+      STARK_TRY(gfail(g, r, fri_fold(g->m[r], (const uint64_t*)f.vals[r], (uint64_t*)p, n, wc, nullptr,
+                                     mtree->d_root(r, G), (uint32_t)G, (uint32_t)r, dig[r], nullptr)));
+    }
+    auto L = std::make_unique<GroupFri::Layer>();
+    STARK_TRY(dtree_commit_digests(g, L->t2, col, q / G, 32, dig));
+    L->mt = mtree;
+    L->q = q;
+    mtree = &L->t2;
+    f.layers.push_back(std::move(L));
+    f.vals = col;
+    n = q;
+    w = F.pow_u64(w, 4);
+    deg /= 4;
+  }
+  f.n = n;
+  f.deg = deg;
+  canon(w, f.wc);
+  if (deg > 16 && n) {  // the rest of prove_low_degree_rec is member 0's: hand the column over on the device
+    void *chunks, *merged;
+    STARK_TRY(take(g, 0, n * 32, &chunks));
+    STARK_TRY(take(g, 0, n * 32, &merged));
+    STARK_TRY(gather_to0(g, f.vals.data(), (uint8_t*)chunks, n / G * 32));
+    STARK_TRY(gfail(g, 0, stark_class_merge_dev(g->m[0], (const uint64_t*)chunks, (uint64_t*)merged, n, (uint32_t)G,
+                                                nullptr)));
+    f.d_tail = (const uint64_t*)merged;
+  }
+  return STARK_OK;
+}
+
+// The top levels of `trees` (the caller's) and of every layer's tree from member 0, and the Last layer's
+// values from every member: one download each, one synchronisation.
+stark_status gfri_download(stark_group* g, GroupFri& f, std::vector<DTree*> trees) {
+  const size_t G = g->m.size();
+  for (auto& L : f.layers) trees.push_back(&L->t2);
+  for (DTree* t : trees) t->host.resize(t->blocked ? (2 * G - 1) * 32 : 32);
+  G_HIP(g, hipSetDevice(g->m[0]->device));
+  for (DTree* t : trees)
+    G_HIP(g, hipMemcpyAsync(t->host.data(), t->levels[0], t->host.size(), hipMemcpyDeviceToHost, stream_of(g, 0)));
+  if (f.deg <= 16) {
+    const size_t nv = f.n / G;
+    f.last_local.resize(G * nv * 32);
+    for (size_t r = 0; r < G && nv; ++r) {
+      G_HIP(g, hipSetDevice(g->m[r]->device));
+      G_HIP(g, hipMemcpyAsync(f.last_local.data() + r * nv * 32, f.vals[r], nv * 32, hipMemcpyDeviceToHost,
+                              stream_of(g, r)));
+    }
+  }
+  return sync_all(g);
+}
+
+// The layers' openings (two per layer at o[2 l], o[2 l + 1]): each layer's ys from its root2.
+stark_status gfri_plan(stark_group* g, const GroupFri& f, DOpen* o) {
+  const size_t G = g->m.size();
+  for (size_t li = 0; li < f.layers.size(); ++li) {
+    const GroupFri::Layer& L = *f.layers[li];
+    std::vector<size_t> ys, poly;
+    STARK_TRY(indices(L.t2.root(), L.q, 40, f.excl, ys));  // fri.rs:181-189
+    for (size_t y : ys)
+      for (size_t j = 0; j < 4; ++j) poly.push_back(y + L.q * j);  // fri.rs:193-204
+    dopen_plan(o[2 * li], L.t2, ys, G);
+    dopen_plan(o[2 * li + 1], *L.mt, poly, G);
+  }
+  return STARK_OK;
+}
+
+// The Vec<FriProof>: the distributed layers from their (assembled) openings, then Last or member 0's tail.
+stark_status gfri_finish(stark_group* g, GroupFri& f, DOpen* o, stark_fri_proof** out) {
+  const size_t G = g->m.size();
+  auto fri = std::make_unique<stark_fri_proof>();
+  for (size_t li = 0; li < f.layers.size(); ++li) {
+    stark_fri_layer L;
+    memcpy(L.root2, f.layers[li]->t2.root(), 32);
+    DOpen& c = o[2 * li];
+    DOpen& p = o[2 * li + 1];
+    L.col_idx = c.idx;
+    L.poly_idx = p.idx;
+    L.col_depth = log2_exact(f.layers[li]->t2.n);
+    L.poly_depth = log2_exact(f.layers[li]->mt->n);
+    L.col_leaves = std::move(c.leaves);
+    L.col_nodes = std::move(c.nodes);
+    L.poly_leaves = std::move(p.leaves);
+    L.poly_nodes = std::move(p.nodes);
+    fri->layers.push_back(std::move(L));
+  }
+  if (f.deg <= 16) {  // fri.rs:65-77: Last, in natural order (value r + G j is member r's j-th)
+    const size_t nv = f.n / G;
+    stark_fri_layer L;
+    L.last = true;
+    L.last_values.resize(f.n * 32);
+    const unsigned nt = (unsigned)std::min<size_t>(host_threads(), std::max<size_t>(nv >> 12, 1));
+    host_parallel(nt, [&](unsigned t) {
+      for (size_t j = nv * t / nt; j < nv * (t + 1) / nt; ++j)
+        for (size_t r = 0; r < G; ++r)
+          memcpy(L.last_values.data() + (r + G * j) * 32, f.last_local.data() + (r * nv + j) * 32, 32);
+    });
+    fri->layers.push_back(std::move(L));
+  } else {
+    stark_fri_proof* tail = nullptr;
+    STARK_TRY(gfail(g, 0, stark_prove_low_degree_dev(g->m[0], f.d_tail, f.n, f.wc, f.deg, f.excl, &tail)));
+    for (auto& L : tail->layers) fri->layers.push_back(std::move(L));
+    stark_fri_proof_free(tail);
+  }
+  *out = fri.release();
+  return STARK_OK;
+}
+
+// prove_low_degree over the group from class-distributed values (cls[r]: member r's n / G, not modified).
+stark_status group_fri(stark_group* g, const std::vector<const uint8_t*>& cls, size_t n, const uint64_t root[4],
+                       size_t deg, uint32_t excl, stark_fri_proof** out) {
+  const size_t G = g->m.size();
+  DTree vt;
+  STARK_TRY(dtree_commit(g, vt, cls, n / G, 32));
+  GroupFri f;
+  STARK_TRY(gfri_commit(g, cls, &vt, n, root, deg, excl, f));
+  STARK_TRY(gfri_download(g, f, {&vt}));
+  std::vector<DOpen> opens(2 * f.layers.size());
+  STARK_TRY(gfri_plan(g, f, opens.data()));
+  STARK_TRY(open_all(g, opens));
+  return gfri_finish(g, f, opens.data(), out);
+}
+
+// Small inputs are member 0's: the class chunks gathered there and merged into natural order.
+stark_status group_fri_on0(stark_group* g, const uint64_t* const* d_class, size_t n, const uint64_t root[4],
+                           size_t deg, uint32_t excl, stark_fri_proof** out) {
+  const size_t G = g->m.size();
+  if (G == 1 || n == 0) return gfail(g, 0, stark_prove_low_degree_dev(g->m[0], d_class[0], n, root, deg, excl, out));
+  void *chunks, *merged;
+  STARK_TRY(take(g, 0, n * 32, &chunks));
+  STARK_TRY(take(g, 0, n * 32, &merged));
+  std::vector<const uint8_t*> send(G);
+  for (size_t r = 0; r < G; ++r) send[r] = (const uint8_t*)d_class[r];
+  STARK_TRY(gather_to0(g, send.data(), (uint8_t*)chunks, n / G * 32));
+  STARK_TRY(gfail(g, 0, stark_class_merge_dev(g->m[0], (const uint64_t*)chunks, (uint64_t*)merged, n, (uint32_t)G,
+                                              nullptr)));
+  const stark_status st =
+      gfail(g, 0, stark_prove_low_degree_dev(g->m[0], (const uint64_t*)merged, n, root, deg, excl, out));
+  // (the members' streams wait on each other's copies: leave none of them behind the caller's next use)
+  const stark_status ss = sync_all(g);
+  return st != STARK_OK ? st : ss;
+}
+
+bool fri_distributed(size_t G, size_t n, size_t deg) { return G > 1 && n > ((size_t)1 << kFriTailLog) && deg > 16; }
+
 // prove_with_witness (run.rs:310-452) = mk_r1cs_proof (prove.rs:14-378) over the group; begin(r) starts
 // member r's share (trace, coset LDEs, constraints; stark_dprove_begin_*).
 template <class Begin>
 stark_status group_prove(stark_group* g, Begin&& begin, stark_r1cs_proof** out) {
   const size_t G = g->m.size();
-  const FieldHost& F = FieldHost::get();
   reset_cursors(g);
   DProveHandles hs;
   hs.h.assign(G, nullptr);
@@ -603,97 +814,22 @@ stark_status group_prove(stark_group* g, Begin&& begin, stark_r1cs_proof** out) 
     lv[r] = (const uint8_t*)l;
   }
   STARK_TRY(dtree_commit(g, ltree, lv, n_local, 32));
-  // prove_low_degree(L, g2, precision / 4, 8) (prove.rs:367, fri.rs:46-224), layer by layer while the
-  // layers are large; the fold's special_x comes from the previous tree's root on the device
-  struct Layer {
-    DTree t2;
-    const DTree* mt;
-    size_t q;
-  };
-  std::vector<std::unique_ptr<Layer>> layers;
-  std::vector<const uint8_t*> vals = lv;
-  size_t n = P, deg = P / 4;
-  HostFp w = F.from_canonical(g2[0].data());
-  const DTree* mtree = &ltree;
-  while (deg > 16 && n > ((size_t)1 << kFriTailLog)) {
-    const size_t q = n / 4;
-    uint64_t wc[4];
-    canon(w, wc);
-    std::vector<const uint8_t*> col(G);
-    for (size_t r = 0; r < G; ++r) {
-      void* p;
-      STARK_TRY(take(g, r, q / G * 32, &p));
-      col[r] = (const uint8_t*)p;
-      STARK_TRY(gfail(g, r, stark_fri_fold_dev_root(g->m[r], (const uint64_t*)vals[r], (uint64_t*)p, n, wc,
-                                                     mtree->d_root(r, G), (uint32_t)G, (uint32_t)r, nullptr)));
-    }
-    auto L = std::make_unique<Layer>();
-    STARK_TRY(dtree_commit(g, L->t2, col, q / G, 32));
-    L->mt = mtree;
-    L->q = q;
-    mtree = &L->t2;
-    layers.push_back(std::move(L));
-    vals = col;
-    n = q;
-    w = F.pow_u64(w, 4);
-    deg /= 4;
-  }
-  // every tree's top levels (member 0) and the last layer's values (every member), one download each
-  std::vector<DTree*> trees = {&main, &ltree};
-  for (auto& L : layers) trees.push_back(&L->t2);
-  for (DTree* t : trees) t->host.resize(t->blocked ? (2 * G - 1) * 32 : 32);
-  const size_t nv = n / G;
-  std::vector<uint8_t> last_local(G * nv * 32);
-  G_HIP(g, hipSetDevice(g->m[0]->device));
-  for (DTree* t : trees)
-    G_HIP(g, hipMemcpyAsync(t->host.data(), t->levels[0], t->host.size(), hipMemcpyDeviceToHost, stream_of(g, 0)));
-  for (size_t r = 0; r < G; ++r) {
-    G_HIP(g, hipSetDevice(g->m[r]->device));
-    G_HIP(g, hipMemcpyAsync(last_local.data() + r * nv * 32, vals[r], nv * 32, hipMemcpyDeviceToHost,
-                            stream_of(g, r)));
-  }
-  STARK_TRY(sync_all(g));
-  // the transcript: spot-check positions from l_root (prove.rs:337-362), each layer's ys from its root2
+  // prove_low_degree(L, g2, precision / 4, 8) (prove.rs:367, fri.rs:46-224)
   const size_t skips = kExt;
+  GroupFri f;
+  STARK_TRY(gfri_commit(g, lv, &ltree, P, g2[0].data(), P / 4, (uint32_t)skips, f));
+  // every tree's top levels (and a Last layer's values), one download each
+  STARK_TRY(gfri_download(g, f, {&main, &ltree}));
+  // the transcript: spot-check positions from l_root (prove.rs:337-362), each layer's ys from its root2
   std::vector<size_t> positions, aug;
   STARK_TRY(indices(ltree.root(), P, kSpot, (uint32_t)skips, positions));
   aug.resize(4 * positions.size());
   for (size_t i = 0; i < positions.size(); ++i) spot_rows(positions[i], osteps, skips, P, &aug[4 * i]);
-  std::vector<DOpen> opens(2 + 2 * layers.size());
+  std::vector<DOpen> opens(2 + 2 * f.layers.size());
   dopen_plan(opens[0], main, aug, G);
   dopen_plan(opens[1], ltree, positions, G);
-  for (size_t li = 0; li < layers.size(); ++li) {
-    const Layer& L = *layers[li];
-    std::vector<size_t> ys, poly;
-    STARK_TRY(indices(L.t2.root(), L.q, 40, (uint32_t)skips, ys));  // fri.rs:181-189
-    for (size_t y : ys)
-      for (size_t j = 0; j < 4; ++j) poly.push_back(y + L.q * j);   // fri.rs:193-204
-    dopen_plan(opens[2 + 2 * li], L.t2, ys, G);
-    dopen_plan(opens[3 + 2 * li], *L.mt, poly, G);
-  }
-  // every member gathers what it holds in one zero-copy launch
-  STARK_TRY(for_members(g, [&](size_t r) {
-    std::vector<stark_open_req> reqs;
-    for (DOpen& o : opens) {
-      const DTree& d = *o.d;
-      stark_open_req a{};
-      a.d_rows = d.leaves[r];
-      a.row_bytes = d.leaf_len;
-      a.n_rows = d.nl;
-      a.idx = o.leaf_local[r].data();
-      a.k = o.leaf_local[r].size();
-      a.leaves_out = o.leaf_out[r].data();
-      reqs.push_back(a);
-      stark_open_req b{};
-      b.tree = d.t[r];
-      b.idx = o.path_local[r].data();
-      b.k = o.path_local[r].size();
-      b.nodes_out = o.path_out[r].data();
-      reqs.push_back(b);
-    }
-    return stark_open_batch(g->m[r], reqs.data(), reqs.size(), nullptr);
-  }));
-  for (DOpen& o : opens) dopen_assemble(o, G);
+  STARK_TRY(gfri_plan(g, f, opens.data() + 2));
+  STARK_TRY(open_all(g, opens));
   // the proof
   auto proof = std::make_unique<stark_r1cs_proof>();
   memcpy(proof->a_root, a_root[0].data(), 32);
@@ -704,41 +840,7 @@ stark_status group_prove(stark_group* g, Begin&& begin, stark_r1cs_proof** out) 
   proof->m_nodes = std::move(opens[0].nodes);
   proof->l_leaves = std::move(opens[1].leaves);
   proof->l_nodes = std::move(opens[1].nodes);
-  auto fri = std::make_unique<stark_fri_proof>();
-  for (size_t li = 0; li < layers.size(); ++li) {
-    stark_fri_layer L;
-    memcpy(L.root2, layers[li]->t2.root(), 32);
-    DOpen& c = opens[2 + 2 * li];
-    DOpen& p = opens[3 + 2 * li];
-    L.col_idx = c.idx;
-    L.poly_idx = p.idx;
-    L.col_depth = log2_exact(layers[li]->t2.n);
-    L.poly_depth = log2_exact(layers[li]->mt->n);
-    L.col_leaves = std::move(c.leaves);
-    L.col_nodes = std::move(c.nodes);
-    L.poly_leaves = std::move(p.leaves);
-    L.poly_nodes = std::move(p.nodes);
-    fri->layers.push_back(std::move(L));
-  }
-  // the last distributed layer's values in natural order (value r + G j is member r's j-th)
-  std::vector<uint8_t> values(n * 32);
-  for (size_t r = 0; r < G; ++r)
-    for (size_t j = 0; j < nv; ++j) memcpy(values.data() + (r + G * j) * 32, last_local.data() + (r * nv + j) * 32, 32);
-  if (deg <= 16) {  // fri.rs:65-77: Last
-    stark_fri_layer L;
-    L.last = true;
-    L.last_values = std::move(values);
-    fri->layers.push_back(std::move(L));
-  } else {  // the rest of prove_low_degree_rec on member 0
-    uint64_t wc[4];
-    canon(w, wc);
-    stark_fri_proof* tail = nullptr;
-    STARK_TRY(gfail(g, 0, stark_prove_low_degree(g->m[0], (const uint64_t*)values.data(), n, wc, deg,
-                                                 (uint32_t)skips, &tail)));
-    for (auto& L : tail->layers) fri->layers.push_back(std::move(L));
-    stark_fri_proof_free(tail);
-  }
-  proof->fri = fri.release();
+  STARK_TRY(gfri_finish(g, f, opens.data() + 2, &proof->fri));
   render_proof(proof.get(), aug.size(), positions.size());
   *out = proof.release();
   return STARK_OK;
@@ -963,6 +1065,66 @@ stark_status stark_group_merkle_gen_proofs(stark_group_tree* t, const size_t* in
   }
   t->has_root = true;
   return STARK_OK;
+}
+
+stark_status stark_group_prove_low_degree(stark_group* g, const uint64_t* values, size_t n, const uint64_t root[4],
+                                          size_t max_deg_plus_1, uint32_t exclude_multiples_of,
+                                          stark_fri_proof** out) {
+  if (!g || !root || !out || (n && !values)) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  g->last_error.clear();
+  const size_t G = g->m.size();
+  if (!fri_distributed(G, n, max_deg_plus_1))
+    return gfail(g, 0, stark_prove_low_degree(g->m[0], values, n, root, max_deg_plus_1, exclude_multiples_of, out));
+  G_HIP(g, hipSetDevice(g->m[0]->device));
+  STARK_TRY(gfail(g, 0, fri_check(g->m[0], n, root, max_deg_plus_1, exclude_multiples_of, nullptr, nullptr)));
+  reset_cursors(g);
+  // Member b uploads the block values[b n/G, (b+1) n/G) straight from the caller's memory and deals it
+  // into G class chunks; one all-to-all then leaves member r with class r in order: block b's chunk r is
+  // values[b n/G + r + G j'], class indices b n/G/G + j'.
+  const size_t nb = n / G, chunk = nb / G * sizeof(fe);
+  std::vector<uint8_t*> block(G), dealt(G), cls(G);
+  for (size_t r = 0; r < G; ++r) {
+    void* p;
+    STARK_TRY(take(g, r, nb * sizeof(fe), &p));
+    block[r] = (uint8_t*)p;
+    STARK_TRY(take(g, r, nb * sizeof(fe), &p));
+    dealt[r] = (uint8_t*)p;
+    STARK_TRY(take(g, r, nb * sizeof(fe), &p));
+    cls[r] = (uint8_t*)p;
+  }
+  STARK_TRY(for_members(g, [&](size_t r) {
+    stark_ctx* c = g->m[r];
+    STARK_HIP(c, hipSetDevice(c->device));
+    STARK_HIP(c, hipMemcpyAsync(block[r], values + 4 * r * nb, nb * sizeof(fe), hipMemcpyHostToDevice, c->stream));
+    return stark_class_deal_dev(c, (const uint64_t*)block[r], (uint64_t*)dealt[r], nb, (uint32_t)G, nullptr);
+  }));
+  std::vector<const uint8_t*> send(dealt.begin(), dealt.end());
+  STARK_TRY(exchange(g, send.data(), cls.data(), chunk, false));
+  const stark_status st = group_fri(g, std::vector<const uint8_t*>(cls.begin(), cls.end()), n, root, max_deg_plus_1,
+                                    exclude_multiples_of, out);
+  if (st != STARK_OK) sync_all(g);  // (the uploads read the caller's memory)
+  return st;
+}
+
+stark_status stark_group_prove_low_degree_dev(stark_group* g, const uint64_t* const* d_class, size_t n,
+                                              const uint64_t root[4], size_t max_deg_plus_1,
+                                              uint32_t exclude_multiples_of, stark_fri_proof** out) {
+  if (!g || !root || !out || !d_class) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  g->last_error.clear();
+  const size_t G = g->m.size();
+  for (size_t r = 0; r < G && n; ++r)
+    if (!d_class[r]) return STARK_ERR_BAD_ARG;
+  G_HIP(g, hipSetDevice(g->m[0]->device));
+  STARK_TRY(gfail(g, 0, fri_check(g->m[0], n, root, max_deg_plus_1, exclude_multiples_of, nullptr, nullptr)));
+  if (n % G != 0) return STARK_ERR_BAD_LENGTH;  // (no class layout: only a Last layer of such a length passes the checks)
+  reset_cursors(g);
+  if (!fri_distributed(G, n, max_deg_plus_1))
+    return group_fri_on0(g, d_class, n, root, max_deg_plus_1, exclude_multiples_of, out);
+  std::vector<const uint8_t*> cls(G);
+  for (size_t r = 0; r < G; ++r) cls[r] = (const uint8_t*)d_class[r];
+  return group_fri(g, cls, n, root, max_deg_plus_1, exclude_multiples_of, out);
 }
 
 stark_status stark_group_prove_r1cs_bytes(stark_group* g, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* wtns,

@@ -553,6 +553,43 @@ stark_status fri_enqueue(stark_ctx* ctx, const fe* d_values, size_t n, const uin
 stark_status fri_finish(stark_ctx* ctx, FriPending* p, std::vector<GatherReq>& extra, stark_fri_proof** out);
 stark_status fri_prove_device(stark_ctx* ctx, const fe* d_values, size_t n, const uint64_t root[4],
                               size_t max_deg_plus_1, uint32_t excl, stark_fri_proof** out);
+// prove_low_degree's argument checks alone (fri.hip): the status fri_enqueue returns for these arguments
+// before it enqueues anything.  n_layers / tw_out may be null.
+stark_status fri_check(stark_ctx* ctx, size_t n, const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,
+                       size_t* n_layers, const Twiddles** tw_out);
+// One FRI fold on a residue class (stark_fri_fold_dev / _dev_root, fri.hip): special_x from a host root
+// (m_root) or a device-resident one (d_m_root).  d_digests non-null: the launch also writes the Blake2s of
+// each folded value (n / (4 world) x 32 B, 16-B aligned), the leaf digests of the column's tree.
+stark_status fri_fold(stark_ctx* ctx, const uint64_t* values, uint64_t* column, size_t n, const uint64_t root[4],
+                      const uint8_t* m_root, const uint8_t* d_m_root, uint32_t world, uint32_t rank,
+                      uint8_t* d_digests, void* stream);
+
+// A Merkle tree over n leaves held by residue class over a group's members (member r: leaves r + G j),
+// stark_amd/dprove.py DistTree (group.hip): digests hashed where the leaves are, one all-to-all of
+// digests, member s builds the subtree of leaves [s nl, (s+1) nl), the subtree roots gathered to every
+// member, and the top levels hashed on each (every member's next step reads the root on its own stream).
+struct DTree {
+  bool blocked = false;
+  size_t n = 0, nl = 0, leaf_len = 0;
+  std::vector<const uint8_t*> leaves;
+  std::vector<stark_merkle_tree*> t;
+  std::vector<uint8_t*> levels;  // blocked: G roots then the G - 1 above (root last); else the root
+  std::vector<uint8_t> host;
+  const uint8_t* d_root(size_t r, size_t G) const { return levels[r] + (blocked ? (2 * G - 2) * 32 : 0); }
+  const uint8_t* root() const { return host.data() + host.size() - 32; }
+  size_t level_width(size_t G, uint32_t lvl) const { return G >> lvl; }
+  const uint8_t* level_node(size_t G, uint32_t lvl, size_t i) const {
+    size_t at = 0;
+    for (uint32_t l = 0; l < lvl; ++l) at += G >> l;
+    return host.data() + 32 * (at + i);
+  }
+};
+// leaves[r]: member r's nl leaves of leaf_len bytes (device).  dtree_commit hashes them;
+// dtree_commit_digests takes their digests ready (digests[r]: nl x 32 B on member r, e.g. fri_fold's).
+stark_status dtree_commit(stark_group* g, DTree& d, const std::vector<const uint8_t*>& leaves, size_t nl,
+                          size_t leaf_len);
+stark_status dtree_commit_digests(stark_group* g, DTree& d, const std::vector<const uint8_t*>& leaves, size_t nl,
+                                  size_t leaf_len, const std::vector<uint8_t*>& digests);
 
 // Montgomery image of a host value as a device fe (same bytes).
 inline fe to_dev(const HostFp& x) {

@@ -114,6 +114,8 @@ _SIGNATURES = {
     "stark_ntt_strided_tw_dev": ([_vp, _vp, ctypes.c_uint32, ctypes.c_size_t, _u64p, ctypes.c_int, _u64p,
                                   ctypes.c_uint32, ctypes.c_uint64, _vp], ctypes.c_int),
     "stark_transpose_dev": ([_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, _vp], ctypes.c_int),
+    "stark_class_deal_dev": ([_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_uint32, _vp], ctypes.c_int),
+    "stark_class_merge_dev": ([_vp, _vp, _vp, ctypes.c_size_t, ctypes.c_uint32, _vp], ctypes.c_int),
     "stark_twiddle2d_dev": ([_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64, _u64p,
                              ctypes.c_uint32, _vp], ctypes.c_int),
     "stark_dev_alloc": ([_vp, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
@@ -174,6 +176,10 @@ _SIGNATURES = {
     "stark_group_merkle_width": ([_vp], ctypes.c_size_t),
     "stark_group_merkle_get_root": ([_vp, ctypes.c_char_p, _szp], ctypes.c_int),
     "stark_group_merkle_gen_proofs": ([_vp, _szp, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p], ctypes.c_int),
+    "stark_group_prove_low_degree": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, ctypes.c_uint32,
+                                      ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_group_prove_low_degree_dev": ([_vp, ctypes.POINTER(_vp), ctypes.c_size_t, _u64p, ctypes.c_size_t,
+                                          ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_group_prove_r1cs_bytes": ([_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                       ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_group_circuit_new": ([_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
@@ -367,6 +373,16 @@ class Context:
 
     def transpose_dev(self, d_src: int, d_dst: int, rows: int, cols: int, batch: int = 1, stream: int = 0) -> None:
         self.check(self.lib.stark_transpose_dev(self.h, d_src, d_dst, rows, cols, batch, stream or None), "transpose")
+
+    def class_deal_dev(self, d_block: int, d_chunks: int, n_block: int, world: int, stream: int = 0) -> None:
+        """chunk r, element j = block[r + world j] (stark_class_deal_dev)."""
+        self.check(self.lib.stark_class_deal_dev(self.h, d_block, d_chunks, n_block, world, stream or None),
+                   "class_deal")
+
+    def class_merge_dev(self, d_chunks: int, d_block: int, n_block: int, world: int, stream: int = 0) -> None:
+        """block[r + world j] = chunk r, element j (stark_class_merge_dev)."""
+        self.check(self.lib.stark_class_merge_dev(self.h, d_chunks, d_block, n_block, world, stream or None),
+                   "class_merge")
 
     def twiddle2d_dev(self, d_ptr: int, rows: int, cols: int, row_base: int, col_base: int, root, log_order: int,
                       stream: int = 0) -> None:

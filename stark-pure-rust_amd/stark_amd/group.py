@@ -7,6 +7,7 @@ names and return what the single-context calls return, bit for bit:
 
     Group.best_fft / inv_best_fft          fft.rs:327-379 (one-exchange cyclic NTT across members)
     Group.merkle() -> GroupMerkleTree      MerkleTree trait, merkle_tree.rs:60-73 (subtree + top tree)
+    Group.prove_low_degree (/ _dev)        fri.rs:46-62 (class-local folds, one digest all-to-all per tree)
     Group.prove_with_witness               run.rs:310-452 (one proof shared by the members)
     Group.circuit(r1cs).prove(wtns)        the same with the .r1cs-only work prepared once
 
@@ -21,7 +22,7 @@ import ctypes
 
 import numpy as np
 
-from . import Proof, StarkError, _elems, _limbs, _out_array, _p64, _vp, load_library
+from . import FriProofList, Proof, StarkError, _elems, _limbs, _out_array, _p64, _vp, load_library
 
 
 def _lib():
@@ -91,6 +92,27 @@ class Group:
     # ---- commitment ---------------------------------------------------------------------------
     def merkle(self) -> "GroupMerkleTree":
         return GroupMerkleTree(self)
+
+    # ---- fri::fri -----------------------------------------------------------------------------
+    def prove_low_degree(self, values, root_of_unity, max_deg_plus_1: int, exclude_multiples_of: int):
+        """fri.rs:46-62 over the group.  Returns the FriProofList Context.prove_low_degree returns."""
+        v = _elems(values)
+        h = _vp()
+        self.check(self.lib.stark_group_prove_low_degree(self.h, _p64(v), len(v), _p64(_limbs(root_of_unity)),
+                                                         max_deg_plus_1, exclude_multiples_of, ctypes.byref(h)),
+                   "group_prove_low_degree")
+        return FriProofList(self.lib, h)
+
+    def prove_low_degree_dev(self, class_ptrs, n: int, root_of_unity, max_deg_plus_1: int,
+                             exclude_multiples_of: int):
+        """The same on values already on the members: class_ptrs[r] = member r's device pointer to
+        values[r + G j], j < n / G (not modified)."""
+        a = (_vp * self.G)(*[int(p) if p else None for p in class_ptrs])
+        h = _vp()
+        self.check(self.lib.stark_group_prove_low_degree_dev(self.h, a, n, _p64(_limbs(root_of_unity)),
+                                                             max_deg_plus_1, exclude_multiples_of, ctypes.byref(h)),
+                   "group_prove_low_degree_dev")
+        return FriProofList(self.lib, h)
 
     # ---- r1cs-stark ---------------------------------------------------------------------------
     def prove_with_witness(self, r1cs: bytes, wtns: bytes):
