@@ -36,8 +36,10 @@ extern "C" {
 
 /* 2: stark_r1cs_proof_branches takes leaves_cap / nodes_cap (round 4).
  * 3: device groups, stark_group_* (round 6).
- * 4: stark_group_prove_low_degree(_dev), stark_class_deal_dev / stark_class_merge_dev. */
-#define STARK_ABI_VERSION 4u
+ * 4: stark_group_prove_low_degree(_dev), stark_class_deal_dev / stark_class_merge_dev.
+ * 5: stark_zpoly, stark_lagrange_interp(_domain), stark_mul_polys / stark_div_polys,
+ *    stark_ctx_set_public_column_min. */
+#define STARK_ABI_VERSION 5u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -90,6 +92,15 @@ void* stark_ctx_stream(stark_ctx* ctx);
  * not fit is not cached (the NTT's last pass then forms its twiddles from the two-level tables, same
  * outputs).  Setting a lower cap frees down to it at once. */
 stark_status stark_ctx_set_cache_limit(stark_ctx* ctx, size_t bytes);
+/* From how many public points (public_first_indices entries) proofs and verifications on this context take
+ * the column route (no reference counterpart: the reference multiplies Zb2 out and evaluates I2 by Horner at
+ * every point, r1cs-stark/src/utils.rs:421-455, and interpolates in O(m^2), fri/src/poly_utils.rs:409-439).
+ * With m points or more, and fewer than the trace's steps, the prover takes Zb2's and I2's coefficients from
+ * the subproduct tree (stark_zpoly / stark_lagrange_interp's) and extends them like every other column, and
+ * the verifier interpolates on the GPU; the proofs and verdicts are the same either way.  0 restores the
+ * defaults (measured, DESIGN.md 5.4: 128 points for a proof, 1,024 for a verification), SIZE_MAX means
+ * never.  A prepared circuit keeps the 1 / Zb2 it was built with. */
+stark_status stark_ctx_set_public_column_min(stark_ctx* ctx, size_t m);
 /* Device bytes the context holds: cached tables (<= *cache_limit), and everything resident
  * (cached tables, the small per-root twiddle tables, working arenas, context-owned trees).  Any
  * pointer may be NULL. */
@@ -164,6 +175,32 @@ stark_status stark_lincomb(stark_ctx* ctx, const uint64_t* cols, uint32_t n_cols
 /* Device-resident form (columns back to back at d_cols); synchronous. */
 stark_status stark_lincomb_dev(stark_ctx* ctx, const uint64_t* d_cols, uint32_t n_cols, size_t n,
                                const uint64_t* coeffs, uint64_t* d_out, void* stream);
+
+/* zpoly<T>(xs) -> Vec<T> (poly_utils.rs:362-373): the n + 1 coefficients of prod_i (X - xs[i]), low degree
+ * first, out[n] = 1; n = 0 gives [1].  A subproduct tree on the GPU (any n; repeated points allowed). */
+stark_status stark_zpoly(stark_ctx* ctx, const uint64_t* xs, size_t n, uint64_t* out);
+/* lagrange_interp<T>(xs, ys) -> Vec<T> (poly_utils.rs:409-439): the n coefficients, low degree first, of
+ * sum_i ys[i] inv(den_i) zpoly(xs) / (X - xs[i]), den_i = prod_(j != i) (xs[i] - xs[j]); a repeated x has
+ * den = 0, which multi_inv maps to 0, so its points contribute nothing, as in the reference. */
+stark_status stark_lagrange_interp(stark_ctx* ctx, const uint64_t* xs, const uint64_t* ys, size_t n, uint64_t* out);
+/* The same for points that are powers of a primitive 2^log_order-th root, xs[i] = root^exps[i]
+ * (exps[i] < 2^log_order, else STARK_ERR_BAD_ARG; STARK_ERR_BAD_ROOT for another root): the prover's case,
+ * x_k = g1^w_k (r1cs-stark/src/utils.rs:421-436).  The denominators are then one transform of that size
+ * and a gather instead of n Horner evaluations; the result is the same. */
+stark_status stark_lagrange_interp_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order,
+                                          const uint64_t* exps, const uint64_t* ys, size_t n, uint64_t* out);
+
+/* ---- DFT polynomial products (packages/fri/src/fft.rs) --------------------- */
+/* mul_polys<T>(a, b, root_of_unity) -> Vec<T> (fft.rs:381-395): a (la coefficients) and b (lb) zero-padded
+ * to n = 2^log_n, transformed, multiplied pointwise and transformed back: the n coefficients of the cyclic
+ * product a b mod (X^n - 1) (fft.rs:397-415's second case wraps).  root must be a primitive 2^log_n-th
+ * root (STARK_ERR_BAD_ROOT); la, lb <= n (STARK_ERR_BAD_LENGTH). */
+stark_status stark_mul_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
+                             const uint64_t root[4], uint32_t log_n, uint64_t* out);
+/* div_polys<T>(a, b, root_of_unity) -> Vec<T> (fft.rs:419-432): the same with multi_inv of b's transform
+ * (a zero of it maps to zero). */
+stark_status stark_div_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
+                             const uint64_t root[4], uint32_t log_n, uint64_t* out);
 
 /* ---- Blake2s + index sampler (packages/fri/src/utils.rs) ------------------ */
 /* blake(message) -> Vec<u8> (fri/src/utils.rs:5-10): Blake2s-256, unkeyed. */

@@ -331,7 +331,7 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   if (ctx->aux) hipStreamDestroy(ctx->aux);
   ctx->fri_trees.clear();
   for (DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena, &ctx->trace_raw, &ctx->fri_misc,
-                     &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot}) {
+                     &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly}) {
     if (b->ptr) hipFree(b->ptr);
     if (b->ev) hipEventDestroy(b->ev);
   }
@@ -349,6 +349,12 @@ stark_status stark_ctx_set_cache_limit(stark_ctx* ctx, size_t bytes) {
   return STARK_OK;
 }
 
+stark_status stark_ctx_set_public_column_min(stark_ctx* ctx, size_t m) {
+  if (!ctx) return STARK_ERR_BAD_ARG;
+  ctx->public_column_min = m;
+  return STARK_OK;
+}
+
 stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t* cache_limit,
                               size_t* resident_bytes) {
   if (!ctx) return STARK_ERR_BAD_ARG;
@@ -357,7 +363,7 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   for (const auto& kv : ctx->tw) total += kv.second->base_bytes;
   for (const DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena,
                           &ctx->trace_raw, &ctx->fri_misc, &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde,
-                          &ctx->ext_idx_tmp, &ctx->spot})
+                          &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly})
     total += b->ptr ? b->bytes : 0;
   for (const stark_merkle_tree* t : ctx->trees) total += merkle_device_bytes(t);
   for (const stark_merkle_tree* t : ctx->fri_trees) total += merkle_device_bytes(t);

@@ -323,6 +323,15 @@ fe* multi_inv_h_top(stark_ctx* ctx, int k) {  // pinned slot 1: [2560 + 512 k, 3
   return (fe*)(pinned + kPinned1InvTopOff + 512 * (size_t)k);
 }
 
+stark_status eval_poly_device(stark_ctx* ctx, const fe* d_poly, uint64_t deg_plus_1, const fe* d_xs, uint64_t n,
+                              fe* d_out, hipStream_t s) {
+  if (n == 0) return STARK_OK;
+  hipLaunchKernelGGL(eval_poly_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_poly, deg_plus_1, d_xs, n,
+                     d_out, mont_consts());
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
 stark_status multi_inv_device(stark_ctx* ctx, const fe* d_in, fe* d_out, uint64_t n, hipStream_t s) {
   if (n == 0) return STARK_OK;
   fe* h_top = multi_inv_h_top(ctx, 0);

@@ -135,6 +135,12 @@ struct CacheBuf {
 // Default cap on a context's cached tables (the last-pass full twiddle tables, 2^log_n x 32 B per
 // direction, and the shared IDX extensions): both directions of a 2^26 transform.
 constexpr size_t kDefaultCacheLimit = (size_t)4 << 30;
+// Public points from which I2 and Zb2 are columns by default (stark_ctx_set_public_column_min): the smallest
+// measured count at which that route wins at 2^13 and at 2^17 steps, for the prover and, with its fixed cost
+// of a device round trip against a host interpolation that is small below it, for the verifier
+// (profiles/public_column_ab.txt).
+constexpr size_t kDefaultPublicColumnMin = 128;
+constexpr size_t kDefaultVerifyColumnMin = 1024;
 
 }  // namespace stark
 
@@ -154,6 +160,7 @@ struct stark_ctx {
   stark::DevBuf ext_idx_tmp;  // an IDX extension too large for the cache cap (this proof only)
   stark::DevBuf inv_tmp;      // the scratch of a second batch inverse sharing a host round trip (r1cs.hip)
   stark::DevBuf spot;         // circuit_spot_values' tables and sums (r1cs.hip)
+  stark::DevBuf poly;         // the subproduct tree and the interpolation's working set (poly.hip)
   // Merkle trees reused across calls: [0, 1] FRI layer ping-pong, [2..4] the
   // accumulator, main and linear-combination trees of mk_r1cs_proof.
   stark_merkle_tree* trees[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -183,6 +190,9 @@ struct stark_ctx {
   // ones are freed first (stark::cache_reserve).  stark_ctx_set_cache_limit changes it.
   size_t cache_limit = stark::kDefaultCacheLimit;
   uint64_t cache_clock = 0;
+  // Public points from which proofs and verifications take the column route (stark_ctx_set_public_column_min);
+  // 0: stark::kDefaultPublicColumnMin.
+  size_t public_column_min = 0;
 };
 
 namespace stark {
@@ -254,6 +264,37 @@ void multi_inv_top(const InvPlan& plan);
 stark_status multi_inv_down(stark_ctx* ctx, const InvPlan& plan, hipStream_t s);
 fe* multi_inv_h_top(stark_ctx* ctx, int k);  // top array k < 2 in pinned slot 1 (null: no pinned memory)
 stark_status multi_inv_device(stark_ctx* ctx, const fe* d_in, fe* d_out, uint64_t n, hipStream_t s);
+// out[i] = sum_k poly[k] xs[i]^k on device buffers (Horner, one point per thread; field_ops.hip).
+stark_status eval_poly_device(stark_ctx* ctx, const fe* d_poly, uint64_t deg_plus_1, const fe* d_xs, uint64_t n,
+                              fe* d_out, hipStream_t s);
+
+// The subproduct tree of zpoly / lagrange_interp (poly.hip): n points padded to N = 2^log_N, the top's
+// coefficients in z (N), and the transforms of each of the `levels` NTT levels in zt (2 N per level).
+struct PolyTree {
+  size_t n = 0, N = 0;
+  uint32_t log_N = 0, levels = 0;
+  fe *z = nullptr, *zt = nullptr;
+};
+void poly_tree_plan(size_t n, PolyTree& t);
+size_t poly_tree_elems(const PolyTree& t);  // elements of device memory a tree takes
+stark_status poly_tree_build(stark_ctx* ctx, const fe* d_xs, PolyTree& t, fe* mem, hipStream_t s);
+stark_status poly_tree_zpoly(stark_ctx* ctx, const PolyTree& t, fe* d_out, hipStream_t s);  // n + 1 coefficients
+// The points are powers of a 2^log_order-th root: x_i = root^d_exps[i] (device exponents below the order;
+// tw = the root's tables).  Z'(x_i) is then one transform of that size and a gather.
+struct DomainHint {
+  const Twiddles* tw = nullptr;
+  uint32_t log_order = 0;
+  const uint64_t* d_exps = nullptr;
+};
+// lagrange_interp (poly_utils.rs:409-439) on device buffers (canonical): n coefficients into d_out.  mem holds
+// lagrange_scratch_elems(n, hint) elements; *z_out (optional) receives where zpoly(xs)'s n + 1 coefficients
+// are in mem.  Asynchronous on s but for the batch inverse's host round trip.
+size_t lagrange_scratch_elems(size_t n, const DomainHint* hint);
+stark_status lagrange_interp_device(stark_ctx* ctx, const fe* d_xs, const fe* d_ys, size_t n, fe* d_out, fe* mem,
+                                    hipStream_t s, const DomainHint* hint, fe** z_out);
+// d_xs[i] = root^d_exps[i], canonical (tw = the root's tables).
+stark_status poly_domain_points(stark_ctx* ctx, const Twiddles& tw, const uint64_t* d_exps, size_t n, fe* d_xs,
+                                hipStream_t s);
 
 // Context-owned Merkle tree slot (created on first use).
 stark_status ctx_tree(stark_ctx* ctx, int slot, stark_merkle_tree** out);

@@ -1,0 +1,458 @@
+// Polynomial machinery on the GPU: zpoly and lagrange_interp (packages/fri/src/poly_utils.rs:362-439) by a
+// subproduct tree, and the DFT mul_polys / div_polys (packages/fri/src/fft.rs:381-432).
+//
+// The tree.  n points are padded with points x = 0 to N = max(kLeaf, the next power of two): every node of
+// level l is then monic of degree exactly 2^l, stored as its 2^l low coefficients (the leading 1 is
+// implicit), and the padded product is Z(X) X^(N - n): the coefficients of Z are the top's, N - n places up.
+//   levels 0 .. kLeafLog   one launch: each group of kLeaf points is multiplied out factor by factor in LDS
+//                          (poly_leaf_kernel; schoolbook, kLeaf products per coefficient);
+//   level l -> l + 1       the batched forward NTT of size 2^(l+1) over all nodes (the first pass reads the
+//                          2^l coefficients only), one pointwise launch over all pairs, the batched inverse NTT.
+//                          A monic product of degree 2^(l+1) fits that cyclic transform: the leading 1 wraps
+//                          onto coefficient 0.  Neither the implicit 1 nor the wrapped one is ever stored or
+//                          removed: X^(2^l) transforms to (-1)^i and a constant 1 to 1, so the pointwise
+//                          kernels add (+1, -1) to (even, odd) points of a leaf level's transform and
+//                          (0, -2) to a wrapped level's (Adj), and the read-out subtracts the top's 1.
+// The transforms of every level stay in the arena: the interpolation goes up the same tree with
+// N_parent = N_L Z_R + N_R Z_L (degree < 2^(l+1): no wrap), from the leaves' sum_i c_i Z_leaf / (X - x_i),
+// c_i = y_i / Z'(x_i) (the zero-preserving batch inverse: a repeated x has Z'(x) = 0 and drops out, as in
+// the reference, whose numerator then evaluates to 0).  The padded points carry c = 0.
+//
+// The cut-over kLeafLog = 5.  One more level in the leaf kernel costs 2^l more products per point on one
+// dependent chain; one more NTT level costs about 3 (l + 1) products per point (three transforms of two
+// elements per point) but five launches.  By products alone the two meet at l = 4 (16 against 15); the
+// point counts this serves (public inputs: up to ~10^4) make a level's five launches dearer than the
+// 2^18 extra products of l = 5, and at l = 6 the leaf's chain (64 steps of three dependent products) would
+// be longer than those launches.  The choice is by this count, not by a measurement.
+#include "internal.h"
+
+namespace stark {
+
+constexpr uint32_t kLeafLog = 5, kLeaf = 1u << kLeafLog, kPolyThreads = 256;
+static_assert(kPolyThreads % kLeaf == 0, "a leaf group lies in one workgroup");
+
+struct PolyConsts {
+  fe r2;    // R^2 mod p: montmul(x, r2) = Montgomery image of canonical x
+  fe unit;  // canonical 1: montmul(x_m, unit) = canonical x
+};
+
+static PolyConsts poly_consts() {
+  const FieldHost& F = FieldHost::get();
+  PolyConsts c;
+  c.r2 = to_dev(F.from_canonical(F.one().v));
+  c.unit = to_dev(HostFp{{1, 0, 0, 0}});
+  return c;
+}
+
+// What a stored level's transform lacks at even / odd points (canonical).
+struct Adj {
+  fe even, odd;
+};
+static Adj level_adj(bool wrapped) {
+  const FieldHost& F = FieldHost::get();
+  auto canon = [&](const HostFp& m) {
+    HostFp c;
+    F.to_canonical(m, c.v);
+    return to_dev(c);
+  };
+  const HostFp one = F.one(), zero = F.zero();
+  if (!wrapped) return {canon(one), canon(F.sub(zero, one))};
+  return {canon(zero), canon(F.sub(zero, F.add(one, one)))};
+}
+
+// LDS images are limb-major (word w of thread t at w * 256 + t): every access is one dword per lane at
+// consecutive addresses, conflict-free.
+__device__ __forceinline__ void lds_put(uint32_t* a, uint32_t t, const fe& v) {
+#pragma unroll
+  for (int w = 0; w < 8; ++w) a[w * kPolyThreads + t] = v.w[w];
+}
+__device__ __forceinline__ fe lds_get(const uint32_t* a, uint32_t t) {
+  fe v;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) v.w[w] = a[w * kPolyThreads + t];
+  return v;
+}
+
+// Level kLeafLog of the tree from the points: thread j of a group of kLeaf holds coefficient j of
+// Z = prod (X - x_i) and, WITH_N, of N = sum_i c_i Z / (X - x_i), both grown one point at a time:
+//   N <- N (X - x_i) + c_i Z,  Z <- Z (X - x_i)     (coefficient j - 1 comes from the neighbour through LDS).
+// After kLeaf points Z's leading 1 has left the group's kLeaf coefficients.  Points from n on are x = 0, c = 0.
+template <bool WITH_N>
+__global__ __launch_bounds__(kPolyThreads) void poly_leaf_kernel(const fe* __restrict__ xs, const fe* __restrict__ ys,
+                                                                 const fe* __restrict__ inv_den, uint64_t n,
+                                                                 uint64_t N, fe r2, fe* __restrict__ z_out,
+                                                                 fe* __restrict__ n_out) {
+  __shared__ uint32_t xl[8 * kPolyThreads], zl[8 * kPolyThreads];
+  __shared__ uint32_t cl[WITH_N ? 8 * kPolyThreads : 1], nl[WITH_N ? 8 * kPolyThreads : 1];
+  const uint32_t t = threadIdx.x, j = t & (kLeaf - 1), base = t - j;
+  const uint64_t g = (uint64_t)blockIdx.x * kPolyThreads + t;
+  fe x = fe_zero(), c = fe_zero();
+  if (g < n) {
+    x = fe_mul(fe_load(xs + g), r2);
+    if (WITH_N)  // y inv R^-1, then twice by R: the Montgomery image of c
+      c = fe_mul(fe_mul(fe_mul(fe_load(ys + g), fe_load(inv_den + g)), r2), r2);
+  }
+  lds_put(xl, t, x);
+  if (WITH_N) lds_put(cl, t, c);
+  fe z = fe_zero(), nn = fe_zero();
+  if (j == 0) z.w[0] = 1;
+  for (uint32_t i = 0; i < kLeaf; ++i) {
+    lds_put(zl, t, z);
+    if (WITH_N) lds_put(nl, t, nn);
+    __syncthreads();
+    const fe xi = lds_get(xl, base + i);
+    const fe zp = j ? lds_get(zl, t - 1) : fe_zero();
+    if (WITH_N) {
+      const fe np = j ? lds_get(nl, t - 1) : fe_zero();
+      nn = fe_add(fe_sub(np, fe_mul(nn, xi)), fe_mul(z, lds_get(cl, base + i)));
+    }
+    z = fe_sub(zp, fe_mul(z, xi));
+    __syncthreads();
+  }
+  if (g < N) {
+    fe_store(z_out + g, z);
+    if (WITH_N) fe_store(n_out + g, nn);
+  }
+}
+
+// Pair k of a level: out[k][i] = Z_2k^[i] Z_(2k+1)^[i] over transforms of m = 2^log_m points (total = pairs m).
+__global__ void poly_pair_mul_kernel(const fe* __restrict__ zt, uint32_t log_m, uint64_t total, Adj adj, fe r2,
+                                     fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t k = g >> log_m, i = g & (((uint64_t)1 << log_m) - 1);
+  const fe d = (i & 1) ? adj.odd : adj.even;
+  const fe a = fe_add(fe_load(zt + ((2 * k) << log_m) + i), d);
+  const fe b = fe_add(fe_load(zt + ((2 * k + 1) << log_m) + i), d);
+  fe_store(out + g, fe_mul(fe_mul(a, b), r2));
+}
+
+// out[k][i] = N_2k^[i] Z_(2k+1)^[i] + N_(2k+1)^[i] Z_2k^[i].
+__global__ void poly_pair_comb_kernel(const fe* __restrict__ zt, const fe* __restrict__ nt, uint32_t log_m,
+                                      uint64_t total, Adj adj, fe r2, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t k = g >> log_m, i = g & (((uint64_t)1 << log_m) - 1);
+  const uint64_t l = ((2 * k) << log_m) + i, r = ((2 * k + 1) << log_m) + i;
+  const fe d = (i & 1) ? adj.odd : adj.even;
+  const fe zl = fe_add(fe_load(zt + l), d), zr = fe_add(fe_load(zt + r), d);
+  const fe s = fe_add(fe_mul(fe_load(nt + l), zr), fe_mul(fe_load(nt + r), zl));
+  fe_store(out + g, fe_mul(s, r2));
+}
+
+// out[i] = top[i + pad] for i < count (less top_fix at the top's coefficient 0); out[count] = 1 when lead.
+__global__ void poly_readout_kernel(const fe* __restrict__ top, uint64_t pad, uint64_t count, int top_fix, int lead,
+                                    fe* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > count || (i == count && !lead)) return;
+  fe v = fe_zero();
+  v.w[0] = 1;
+  if (i < count) {
+    const fe t = fe_load(top + i + pad);
+    v = (top_fix && i + pad == 0) ? fe_sub(t, v) : t;
+  }
+  fe_store(out + i, v);
+}
+
+// dz[k] = (k + 1) z[k + 1], k < n; dz[k] = 0 for n <= k < fill.
+__global__ void poly_deriv_kernel(const fe* __restrict__ z, uint64_t n, uint64_t fill, fe r2, fe* __restrict__ dz) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= fill) return;
+  fe v = fe_zero();
+  if (k < n) {
+    fe m = fe_zero();
+    m.w[0] = (uint32_t)(k + 1);
+    m.w[1] = (uint32_t)((k + 1) >> 32);
+    v = fe_mul(fe_mul(fe_load(z + k + 1), m), r2);
+  }
+  fe_store(dz + k, v);
+}
+
+// xs[i] = root^exps[i] (canonical) from the root's two-level tables; exps are below the root's order.
+__global__ void poly_domain_points_kernel(const fe* __restrict__ lo, const fe* __restrict__ hi, uint32_t kb,
+                                          const uint64_t* __restrict__ exps, uint64_t n, fe unit,
+                                          fe* __restrict__ xs) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t e = exps[i];
+  fe_store(xs + i, fe_mul(fe_mul(lo[e & (((uint64_t)1 << kb) - 1)], hi[e >> kb]), unit));
+}
+
+__global__ void poly_gather_kernel(const fe* __restrict__ vals, const uint64_t* __restrict__ exps, uint64_t n,
+                                   fe* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) fe_store(out + i, fe_load(vals + exps[i]));
+}
+
+// out[i] = a[i] b[i] (canonical in and out).
+__global__ void poly_pointwise_kernel(const fe* __restrict__ a, const fe* __restrict__ b, uint64_t n, fe r2,
+                                      fe* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) fe_store(out + i, fe_mul(fe_mul(fe_load(a + i), fe_load(b + i)), r2));
+}
+
+static unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
+
+// 7^((p - 1) / 2^k): the primitive 2^k-th root the tree's transforms use (the prover's g2, prove.rs:71-82),
+// and its inverse.
+static stark_status tree_twiddles(stark_ctx* ctx, uint32_t k, const Twiddles** fwd, const Twiddles** inv) {
+  const FieldHost& F = FieldHost::get();
+  static const HostFp w28 = [] {
+    const FieldHost& G = FieldHost::get();
+    uint64_t e[4];
+    memcpy(e, FieldHost::kP, 32);
+    e[0] -= 1;
+    for (int s = 0; s < 28; ++s)
+      for (int l = 0; l < 4; ++l) e[l] = (e[l] >> 1) | (l < 3 ? e[l + 1] << 63 : 0);
+    return G.pow(G.from_u64(7), e, 4);
+  }();
+  if (k > 28) return STARK_ERR_BAD_LENGTH;
+  const HostFp w = F.pow_u64(w28, (uint64_t)1 << (28 - k));
+  uint64_t c[4];
+  F.to_canonical(w, c);
+  STARK_TRY(get_twiddles(ctx, c, k, fwd));
+  F.to_canonical(F.inv(w), c);
+  return get_twiddles(ctx, c, k, inv);
+}
+
+void poly_tree_plan(size_t n, PolyTree& t) {
+  t.n = n;
+  t.log_N = kLeafLog;
+  while (((size_t)1 << t.log_N) < n) ++t.log_N;
+  t.N = (size_t)1 << t.log_N;
+  t.levels = t.log_N - kLeafLog;
+}
+
+size_t poly_tree_elems(const PolyTree& t) { return t.N + 2 * t.N * t.levels; }
+
+// zpoly's tree over the device points xs (canonical): the top in t.z, each level's transforms in t.zt.
+stark_status poly_tree_build(stark_ctx* ctx, const fe* d_xs, PolyTree& t, fe* mem, hipStream_t s) {
+  const PolyConsts pc = poly_consts();
+  t.z = mem;
+  t.zt = mem + t.N;
+  hipLaunchKernelGGL(poly_leaf_kernel<false>, dim3(grid_for(t.N)), dim3(kPolyThreads), 0, s, d_xs, (const fe*)nullptr,
+                     (const fe*)nullptr, (uint64_t)t.n, (uint64_t)t.N, pc.r2, t.z, (fe*)nullptr);
+  STARK_HIP(ctx, hipGetLastError());
+  for (uint32_t lv = 0; lv < t.levels; ++lv) {
+    const uint32_t log_m = kLeafLog + lv + 1;  // the transforms' size: twice the nodes'
+    const uint32_t nodes = (uint32_t)(t.N >> (log_m - 1));
+    const Twiddles *fwd, *inv;
+    STARK_TRY(tree_twiddles(ctx, log_m, &fwd, &inv));
+    fe* zt = t.zt + 2 * t.N * lv;
+    STARK_TRY(ntt_device_from(ctx, t.z, 1, zt, log_m, nodes, *fwd, false, s));
+    hipLaunchKernelGGL(poly_pair_mul_kernel, dim3(grid_for(t.N)), dim3(256), 0, s, (const fe*)zt, log_m,
+                       (uint64_t)t.N, level_adj(lv > 0), pc.r2, t.z);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(ntt_device(ctx, t.z, log_m, nodes / 2, *inv, true, s));
+  }
+  return STARK_OK;
+}
+
+// The n + 1 coefficients of prod (X - x_i) out of a built tree (low degree first, out[n] = 1).
+stark_status poly_tree_zpoly(stark_ctx* ctx, const PolyTree& t, fe* d_out, hipStream_t s) {
+  hipLaunchKernelGGL(poly_readout_kernel, dim3(grid_for(t.n + 1)), dim3(256), 0, s, (const fe*)t.z,
+                     (uint64_t)(t.N - t.n), (uint64_t)t.n, t.levels > 0 ? 1 : 0, 1, d_out);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
+size_t lagrange_scratch_elems(size_t n, const DomainHint* hint) {
+  PolyTree t;
+  poly_tree_plan(n, t);
+  size_t dz = n;
+  if (hint && n <= ((size_t)1 << hint->log_order)) dz = (size_t)1 << hint->log_order;
+  // the tree, N's coefficients and transforms, Z (n + 1), Z', den, 1 / den
+  return poly_tree_elems(t) + 3 * t.N + (n + 1) + dz + 2 * n;
+}
+
+stark_status lagrange_interp_device(stark_ctx* ctx, const fe* d_xs, const fe* d_ys, size_t n, fe* d_out, fe* mem,
+                                    hipStream_t s, const DomainHint* hint, fe** z_out) {
+  if (n == 0) return STARK_OK;
+  const PolyConsts pc = poly_consts();
+  PolyTree t;
+  poly_tree_plan(n, t);
+  if (hint && n > ((size_t)1 << hint->log_order)) hint = nullptr;  // Z' does not fit the domain: Horner
+  const size_t dz_n = hint ? (size_t)1 << hint->log_order : n;
+  fe* at = mem + poly_tree_elems(t);
+  fe* nc = at;         // N's coefficients, level by level
+  fe* nt = nc + t.N;   // their transforms
+  fe* z = nt + 2 * t.N;
+  fe* dz = z + (n + 1);
+  fe* den = dz + dz_n;
+  fe* inv = den + n;
+  STARK_TRY(poly_tree_build(ctx, d_xs, t, mem, s));
+  STARK_TRY(poly_tree_zpoly(ctx, t, z, s));
+  if (z_out) *z_out = z;
+  hipLaunchKernelGGL(poly_deriv_kernel, dim3(grid_for(dz_n)), dim3(256), 0, s, (const fe*)z, (uint64_t)n,
+                     (uint64_t)dz_n, pc.r2, dz);
+  STARK_HIP(ctx, hipGetLastError());
+  if (hint) {  // the points are root^e: Z' over the whole domain by one transform, then a gather
+    STARK_TRY(ntt_device(ctx, dz, hint->log_order, 1, *hint->tw, false, s));
+    hipLaunchKernelGGL(poly_gather_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const fe*)dz, hint->d_exps,
+                       (uint64_t)n, den);
+    STARK_HIP(ctx, hipGetLastError());
+  } else {
+    STARK_TRY(eval_poly_device(ctx, dz, n, d_xs, n, den, s));
+  }
+  STARK_TRY(multi_inv_device(ctx, den, inv, n, s));
+  hipLaunchKernelGGL(poly_leaf_kernel<true>, dim3(grid_for(t.N)), dim3(kPolyThreads), 0, s, d_xs, d_ys,
+                     (const fe*)inv, (uint64_t)n, (uint64_t)t.N, pc.r2, t.z, nc);
+  STARK_HIP(ctx, hipGetLastError());
+  // (t.z is overwritten with the leaf level again: Z's coefficients were read out above, and the levels
+  // above are taken from their kept transforms)
+  for (uint32_t lv = 0; lv < t.levels; ++lv) {
+    const uint32_t log_m = kLeafLog + lv + 1;
+    const uint32_t nodes = (uint32_t)(t.N >> (log_m - 1));
+    const Twiddles *fwd, *tinv;
+    STARK_TRY(tree_twiddles(ctx, log_m, &fwd, &tinv));
+    STARK_TRY(ntt_device_from(ctx, nc, 1, nt, log_m, nodes, *fwd, false, s));
+    hipLaunchKernelGGL(poly_pair_comb_kernel, dim3(grid_for(t.N)), dim3(256), 0, s,
+                       (const fe*)(t.zt + 2 * t.N * lv), (const fe*)nt, log_m, (uint64_t)t.N, level_adj(lv > 0), pc.r2,
+                       nc);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(ntt_device(ctx, nc, log_m, nodes / 2, *tinv, true, s));
+  }
+  hipLaunchKernelGGL(poly_readout_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const fe*)nc, (uint64_t)(t.N - n),
+                     (uint64_t)n, 0, 0, d_out);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
+stark_status poly_domain_points(stark_ctx* ctx, const Twiddles& tw, const uint64_t* d_exps, size_t n, fe* d_xs,
+                                hipStream_t s) {
+  if (n == 0) return STARK_OK;
+  hipLaunchKernelGGL(poly_domain_points_kernel, dim3(grid_for(n)), dim3(256), 0, s, tw.d_lo, tw.d_hi, tw.kb, d_exps,
+                     (uint64_t)n, poly_consts().unit, d_xs);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
+}  // namespace stark
+
+using namespace stark;
+
+namespace {
+
+// mul_polys / div_polys (fft.rs:381-432): both inputs zero-padded to n = 2^log_n and transformed, the
+// pointwise product (div: by multi_inv of b's transform, zeros kept), transformed back.
+stark_status mul_div_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
+                           const uint64_t root[4], uint32_t log_n, uint64_t* out, bool div) {
+  if (!ctx || !root || !out || (la && !a) || (lb && !b)) return STARK_ERR_BAD_ARG;
+  if (log_n > 28) return STARK_ERR_BAD_LENGTH;
+  const size_t n = (size_t)1 << log_n;
+  if (la > n || lb > n) return STARK_ERR_BAD_LENGTH;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const FieldHost& F = FieldHost::get();
+  const Twiddles *fwd = nullptr, *inv = nullptr;
+  STARK_TRY(get_twiddles(ctx, root, log_n, &fwd));
+  uint64_t rinv[4];
+  F.to_canonical(F.inv(F.from_canonical(root)), rinv);
+  STARK_TRY(get_twiddles(ctx, rinv, log_n, &inv));
+  hipStream_t s = ctx->stream;
+  STARK_TRY(ensure_buf(ctx, ctx->io, 3 * n * sizeof(fe)));
+  fe* da = (fe*)ctx->io.ptr;
+  fe* db = da + n;
+  fe* dbi = db + n;
+  if (la) STARK_HIP(ctx, hipMemcpyAsync(da, a, la * sizeof(fe), hipMemcpyHostToDevice, s));
+  if (la < n) STARK_HIP(ctx, hipMemsetAsync(da + la, 0, (n - la) * sizeof(fe), s));
+  if (lb) STARK_HIP(ctx, hipMemcpyAsync(db, b, lb * sizeof(fe), hipMemcpyHostToDevice, s));
+  if (lb < n) STARK_HIP(ctx, hipMemsetAsync(db + lb, 0, (n - lb) * sizeof(fe), s));
+  STARK_TRY(ntt_device(ctx, da, log_n, 2, *fwd, false, s));
+  if (div) STARK_TRY(multi_inv_device(ctx, db, dbi, n, s));
+  hipLaunchKernelGGL(poly_pointwise_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const fe*)da,
+                     (const fe*)(div ? dbi : db), (uint64_t)n, poly_consts().r2, da);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(ntt_device(ctx, da, log_n, 1, *inv, true, s));
+  STARK_HIP(ctx, hipMemcpyAsync(out, da, n * sizeof(fe), hipMemcpyDeviceToHost, s));
+  STARK_HIP(ctx, hipStreamSynchronize(s));
+  return STARK_OK;
+}
+
+// lagrange_interp from host buffers; exps non-null: the points are root^exps[i] (xs is then not read).
+stark_status interp_host(stark_ctx* ctx, const uint64_t* xs, const uint64_t* root, uint32_t log_order,
+                         const uint64_t* exps, const uint64_t* ys, size_t n, uint64_t* out) {
+  if (n == 0) return STARK_OK;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DomainHint hint;
+  if (exps) {
+    if (log_order > 28) return STARK_ERR_BAD_LENGTH;
+    for (size_t i = 0; i < n; ++i)
+      if (exps[i] >> log_order) return STARK_ERR_BAD_ARG;
+    STARK_TRY(get_twiddles(ctx, root, log_order, &hint.tw));
+    hint.log_order = log_order;
+  }
+  // staging: xs, ys, out, the exponents
+  STARK_TRY(ensure_buf(ctx, ctx->io, 3 * n * sizeof(fe) + n * sizeof(uint64_t)));
+  fe* d_xs = (fe*)ctx->io.ptr;
+  fe* d_ys = d_xs + n;
+  fe* d_out = d_ys + n;
+  uint64_t* d_exps = (uint64_t*)(d_out + n);
+  STARK_HIP(ctx, hipMemcpyAsync(d_ys, ys, n * sizeof(fe), hipMemcpyHostToDevice, s));
+  if (exps) {
+    STARK_HIP(ctx, hipMemcpyAsync(d_exps, exps, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    hint.d_exps = d_exps;
+    STARK_TRY(poly_domain_points(ctx, *hint.tw, d_exps, n, d_xs, s));
+  } else {
+    STARK_HIP(ctx, hipMemcpyAsync(d_xs, xs, n * sizeof(fe), hipMemcpyHostToDevice, s));
+  }
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  STARK_TRY(ensure_buf(ctx, ctx->poly, lagrange_scratch_elems(n, exps ? &hint : nullptr) * sizeof(fe)));
+  STARK_TRY(lagrange_interp_device(ctx, d_xs, d_ys, n, d_out, (fe*)ctx->poly.ptr, s, exps ? &hint : nullptr, nullptr));
+  STARK_TRY(buf_release(ctx, ctx->poly, s));
+  STARK_HIP(ctx, hipMemcpyAsync(out, d_out, n * sizeof(fe), hipMemcpyDeviceToHost, s));
+  STARK_HIP(ctx, hipStreamSynchronize(s));
+  return STARK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+stark_status stark_zpoly(stark_ctx* ctx, const uint64_t* xs, size_t n, uint64_t* out) {
+  if (!ctx || !out || (n && !xs)) return STARK_ERR_BAD_ARG;
+  if (n == 0) {
+    out[0] = 1;
+    out[1] = out[2] = out[3] = 0;
+    return STARK_OK;
+  }
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  PolyTree t;
+  poly_tree_plan(n, t);
+  STARK_TRY(ensure_buf(ctx, ctx->io, (2 * n + 1) * sizeof(fe)));
+  fe* d_xs = (fe*)ctx->io.ptr;
+  fe* d_out = d_xs + n;
+  STARK_HIP(ctx, hipMemcpyAsync(d_xs, xs, n * sizeof(fe), hipMemcpyHostToDevice, s));
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  STARK_TRY(ensure_buf(ctx, ctx->poly, poly_tree_elems(t) * sizeof(fe)));
+  STARK_TRY(poly_tree_build(ctx, d_xs, t, (fe*)ctx->poly.ptr, s));
+  STARK_TRY(poly_tree_zpoly(ctx, t, d_out, s));
+  STARK_TRY(buf_release(ctx, ctx->poly, s));
+  STARK_HIP(ctx, hipMemcpyAsync(out, d_out, (n + 1) * sizeof(fe), hipMemcpyDeviceToHost, s));
+  STARK_HIP(ctx, hipStreamSynchronize(s));
+  return STARK_OK;
+}
+
+stark_status stark_lagrange_interp(stark_ctx* ctx, const uint64_t* xs, const uint64_t* ys, size_t n, uint64_t* out) {
+  if (!ctx || (n && (!xs || !ys || !out))) return STARK_ERR_BAD_ARG;
+  return interp_host(ctx, xs, nullptr, 0, nullptr, ys, n, out);
+}
+
+stark_status stark_lagrange_interp_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order,
+                                          const uint64_t* exps, const uint64_t* ys, size_t n, uint64_t* out) {
+  if (!ctx || !root || (n && (!exps || !ys || !out))) return STARK_ERR_BAD_ARG;
+  return interp_host(ctx, nullptr, root, log_order, exps, ys, n, out);
+}
+
+stark_status stark_mul_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
+                             const uint64_t root[4], uint32_t log_n, uint64_t* out) {
+  return mul_div_polys(ctx, a, la, b, lb, root, log_n, out, false);
+}
+
+stark_status stark_div_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
+                             const uint64_t root[4], uint32_t log_n, uint64_t* out) {
+  return mul_div_polys(ctx, a, la, b, lb, root, log_n, out, true);
+}
+
+}  // extern "C"

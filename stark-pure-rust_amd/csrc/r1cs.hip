@@ -432,9 +432,11 @@ __global__ void r1cs_zb_kernel(const fe* __restrict__ lo, const fe* __restrict__
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= prec) return;
   const fe x_m = pow_tab(lo, hi, kb, g_add + (i << log_g));
-  fe acc = one_m;
-  for (uint32_t k = 0; k < npub; ++k) acc = fe_mul(acc, fe_sub(x_m, xpub_m[k]));
-  fe_store(zb2 + i, fe_mul(acc, unit));
+  if (zb2) {  // (null: Zb2 is the extension of its coefficients, the column route)
+    fe acc = one_m;
+    for (uint32_t k = 0; k < npub; ++k) acc = fe_mul(acc, fe_sub(x_m, xpub_m[k]));
+    fe_store(zb2 + i, fe_mul(acc, unit));
+  }
   if (zb3) fe_store(zb3 + i, fe_mul(fe_sub(x_m, xlast_m), unit));  // (null: 1 / Zb3 is the shared column)
 }
 
@@ -450,6 +452,7 @@ struct ConstraintArgs {
   fe pf_coef[8];
   const fe* interp2;     // canonical coefficients, low degree first
   const fe* interp3;
+  const fe* i2_col = nullptr;  // non-null: I2 at this host's points (the column route), read instead of Horner
   const fe* lo;          // g2 tables
   const fe* hi;
   fe* rows;              // precision x 8 elements: rows (plane = 0) or 8 columns of `plane` elements
@@ -536,8 +539,13 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
   // I2 / I3 at x = g2^i (Horner; the interpolants are canonical).
   const fe x_m = pow_tab(a.lo, a.hi, a.kb, gi);
   // (Horner from the leading coefficient: the first step's 0 * x + c is c itself)
-  fe i2 = a.n2 ? a.interp2[a.n2 - 1] : fe_zero();
-  for (uint32_t k = a.n2 ? a.n2 - 1 : 0; k-- > 0;) i2 = fe_add(fe_mul(i2, x_m), a.interp2[k]);
+  fe i2;
+  if (a.i2_col) {  // (uniform)
+    i2 = fe_load(a.i2_col + i);
+  } else {
+    i2 = a.n2 ? a.interp2[a.n2 - 1] : fe_zero();
+    for (uint32_t k = a.n2 ? a.n2 - 1 : 0; k-- > 0;) i2 = fe_add(fe_mul(i2, x_m), a.interp2[k]);
+  }
   fe i3 = a.n3 ? a.interp3[a.n3 - 1] : fe_zero();
   for (uint32_t k = a.n3 ? a.n3 - 1 : 0; k-- > 0;) i3 = fe_add(fe_mul(i3, x_m), a.interp3[k]);
   fe izb2;
@@ -830,11 +838,11 @@ __global__ void coset_scale_kernel(fe* __restrict__ coef, uint32_t log_steps, ui
 // The values of the step columns' polynomials at the points r + 2^log_g j of the precision
 // domain (j < P = precision >> log_g): iNTT(steps, g1), coefficients scaled by g2^(r k), then a
 // P-point NTT with root h = g2^(2^log_g) over the zero-padded coefficients (degree < steps <= P).
-// log_g = r = 0 is the plain LDE of prove.rs:100-101.  coef is destroyed.
-static stark_status coset_lde(stark_ctx* ctx, fe* coef, uint32_t batch, fe* out, uint32_t log_steps,
-                              uint32_t log_prec, uint32_t log_g, uint32_t r, const Twiddles& tw_g1_inv,
-                              const Twiddles& tw_g2, const Twiddles& tw_h, hipStream_t s) {
-  STARK_TRY(ntt_device(ctx, coef, log_steps, batch, tw_g1_inv, true, s));
+// log_g = r = 0 is the plain LDE of prove.rs:100-101.  coef is destroyed.  coset_forward is the half from
+// the coefficients on (columns that are made as coefficients: Zb2 and I2 on the column route).
+static stark_status coset_forward(stark_ctx* ctx, fe* coef, uint32_t batch, fe* out, uint32_t log_steps,
+                                  uint32_t log_prec, uint32_t log_g, uint32_t r, const Twiddles& tw_g2,
+                                  const Twiddles& tw_h, hipStream_t s) {
   if (r) {
     const uint64_t total = (uint64_t)batch << log_steps;
     hipLaunchKernelGGL(coset_scale_kernel, dim3(blocks_for(total)), dim3(256), 0, s, coef, log_steps, total,
@@ -844,6 +852,82 @@ static stark_status coset_lde(stark_ctx* ctx, fe* coef, uint32_t batch, fe* out,
   // best_fft's zero padding (fft.rs:327-357) is implicit: the first pass reads the steps coefficients only.
   const uint32_t log_p = log_prec - log_g;
   return ntt_device_from(ctx, coef, log_p - log_steps, out, log_p, batch, tw_h, false, s);
+}
+static stark_status coset_lde(stark_ctx* ctx, fe* coef, uint32_t batch, fe* out, uint32_t log_steps,
+                              uint32_t log_prec, uint32_t log_g, uint32_t r, const Twiddles& tw_g1_inv,
+                              const Twiddles& tw_g2, const Twiddles& tw_h, hipStream_t s) {
+  STARK_TRY(ntt_device(ctx, coef, log_steps, batch, tw_g1_inv, true, s));
+  return coset_forward(ctx, coef, batch, out, log_steps, log_prec, log_g, r, tw_g2, tw_h, s);
+}
+
+// ---- the public points' columns -----------------------------------------------------------------------
+//
+// With many public wires (stark_ctx_set_public_column_min) Zb2 = prod_k (X - x_k) and the interpolant I2 are
+// what every other polynomial of the proof is: coefficients (from the subproduct tree, poly.hip) extended to
+// the host's points by the forward half of the extension.  The points are x_k = g1^(w_k), w_k the wires'
+// first uses (utils.rs:421-455), so the interpolation's denominators are one steps-point transform.
+
+// Fewer than `steps` points (Zb2 has n + 1 coefficients), at least the context's threshold.
+static bool public_columns(const stark_ctx* ctx, size_t n_pfi, uint64_t steps) {
+  const size_t m = ctx->public_column_min ? ctx->public_column_min : kDefaultPublicColumnMin;
+  return n_pfi > 0 && n_pfi >= m && n_pfi < steps;
+}
+
+// out[k] = in[k] R^-1 (the scale r1cs_zb_kernel stores Zb at: the batch inverse then gives Montgomery images).
+__global__ void scale_rinv_kernel(const fe* __restrict__ in, uint64_t n, fe* __restrict__ out) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  fe unit = fe_zero();
+  unit.w[0] = 1;
+  fe_store(out + k, fe_mul(fe_load(in + k), unit));
+}
+
+// The public points on the device: d_exps[i] = w_i, d_xy = the points g1^(w_i) (n), then, with public_wires,
+// the wires' values (n).  hint names the points for the interpolation.  h is the uploads' host staging: the
+// caller keeps it until its next synchronisation of s.
+static stark_status public_points(stark_ctx* ctx, const HostFp& g2, uint64_t skips, uint32_t log_steps,
+                                  const uint64_t* public_wires, const size_t* pfi, size_t n, uint64_t* d_exps,
+                                  fe* d_xy, DomainHint& hint, std::vector<uint64_t>& h, hipStream_t s) {
+  const FieldHost& F = FieldHost::get();
+  uint64_t g1c[4];
+  F.to_canonical(F.pow_u64(g2, skips), g1c);
+  STARK_TRY(get_twiddles(ctx, g1c, log_steps, &hint.tw));
+  hint.log_order = log_steps;
+  hint.d_exps = d_exps;
+  h.assign(n * (public_wires ? 5 : 1), 0);
+  for (size_t i = 0; i < n; ++i) {
+    h[i] = pfi[2 * i + 1];  // (below steps: stage_dims / circuit_lde)
+    if (public_wires) memcpy(&h[n + 4 * i], public_wires + 4 * pfi[2 * i], 32);
+  }
+  STARK_HIP(ctx, hipMemcpyAsync(d_exps, h.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  if (public_wires)
+    STARK_HIP(ctx, hipMemcpyAsync(d_xy + n, h.data() + n, n * sizeof(fe), hipMemcpyHostToDevice, s));
+  return poly_domain_points(ctx, *hint.tw, d_exps, n, d_xy, s);
+}
+
+// Zb2's coefficients from the tree alone (a prepared circuit: no witness, no interpolation), scaled by R^-1
+// and zero-padded to steps, into coef.  staging: as public_points' h.
+static stark_status public_zb2_coefficients(stark_ctx* ctx, const HostFp& g2, uint64_t skips, uint32_t log_steps,
+                                            const size_t* pfi, size_t n, fe* coef, std::vector<uint64_t>& staging,
+                                            hipStream_t s) {
+  const uint64_t steps = (uint64_t)1 << log_steps;
+  PolyTree t;
+  poly_tree_plan(n, t);
+  // the tree, Z's n + 1 coefficients, the points and their exponents
+  const size_t tree = poly_tree_elems(t);
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  STARK_TRY(ensure_buf(ctx, ctx->poly, (tree + 2 * n + 1) * sizeof(fe) + n * sizeof(uint64_t)));
+  fe* mem = (fe*)ctx->poly.ptr;
+  fe* z = mem + tree;
+  fe* xs = z + n + 1;
+  DomainHint hint;
+  STARK_TRY(public_points(ctx, g2, skips, log_steps, nullptr, pfi, n, (uint64_t*)(xs + n), xs, hint, staging, s));
+  STARK_TRY(poly_tree_build(ctx, xs, t, mem, s));
+  STARK_TRY(poly_tree_zpoly(ctx, t, z, s));
+  STARK_HIP(ctx, hipMemsetAsync(coef, 0, steps * sizeof(fe), s));
+  hipLaunchKernelGGL(scale_rinv_kernel, dim3(blocks_for(n + 1)), dim3(256), 0, s, (const fe*)z, (uint64_t)(n + 1), coef);
+  STARK_HIP(ctx, hipGetLastError());
+  return buf_release(ctx, ctx->poly, s);
 }
 
 // tag 0: IDX[i] = i; tag > 0: F0[i] = 1 for i < tag (calc_flags' flag0, run.rs:283-308), 0 after.
@@ -1082,16 +1166,19 @@ static stark_status proof_roots(stark_ctx* ctx, uint32_t log_steps, uint32_t log
 // The proof's host-side constants (utils.rs:421-474): the boundary points x_k = g2^(skips w_k) of
 // the public wires' first uses (Montgomery, for Zb2), the coefficients of the interpolant I2
 // through (x_k, public value) and of I3 through (x_last, 1) (canonical): 2 n_pfi + 1 elements.
+// with_i2 = false (the column route: the device interpolates, public_coefficients): the 2 n_pfi elements
+// stay zero, unread.
 static std::vector<fe> boundary_consts(const HostFp& g2, uint64_t prec, uint64_t skips, const uint64_t* public_wires,
-                                       const size_t* public_first_indices, size_t n_pfi, HostFp* x_last_out) {
+                                       const size_t* public_first_indices, size_t n_pfi, bool with_i2,
+                                       HostFp* x_last_out) {
   const FieldHost& F = FieldHost::get();
   const HostFp x_last = F.pow_u64(g2, prec - skips);
-  std::vector<HostFp> xv(n_pfi), yv(n_pfi);
-  for (size_t i = 0; i < n_pfi; ++i) {
+  std::vector<HostFp> xv(n_pfi, F.zero()), yv(n_pfi, F.zero());
+  for (size_t i = 0; with_i2 && i < n_pfi; ++i) {
     xv[i] = F.pow_u64(g2, skips * public_first_indices[2 * i + 1]);
     yv[i] = host_fe(public_wires + 4 * public_first_indices[2 * i]);
   }
-  const std::vector<HostFp> interp2 = lagrange_interp(xv, yv);
+  const std::vector<HostFp> interp2 = with_i2 ? lagrange_interp(xv, yv) : xv;
   const std::vector<HostFp> interp3 = lagrange_interp({x_last}, {F.one()});
   auto canon_fe = [&](const HostFp& x) {
     uint64_t c[4];
@@ -1168,6 +1255,10 @@ struct Stage {
   Transcript* d_tr;
   uint32_t nb;     // the scans' blocks
   InvPlan inv_d;   // the batch inverse of A's denominators
+  // The column route (public_columns): Zb2's (times R^-1) and I2's coefficients, steps each, zero-padded,
+  // and I2's extension.
+  bool pub_cols = false;
+  fe *pubc = nullptr, *i2col = nullptr;
 };
 
 static stark_status stage_begin(stark_ctx* ctx, const TraceView& v, const fe* pre, uint32_t world, uint32_t rank,
@@ -1184,6 +1275,7 @@ static stark_status stage_begin(stark_ctx* ctx, const TraceView& v, const fe* pr
   if (st.sc.tinv && st.sc.izb3 &&
       zb2_partial_fractions(st.roots.g2, d.prec, d.skips, d.log_g, v.pfi, v.n_pfi, st.ca))
     st.ca.tinv = st.sc.tinv;
+  st.pub_cols = public_columns(ctx, v.n_pfi, d.steps);
   return STARK_OK;
 }
 
@@ -1209,9 +1301,48 @@ static stark_status stage_buffers(stark_ctx* ctx, const TraceView& v, Stage& st,
   cv.add(&st.rows, 8 * P);
   cv.add(&st.lvals, P);
   cv.add(&st.d_tr, 1);
+  if (st.pub_cols) {
+    cv.add(&st.pubc, 2 * steps);
+    cv.add(&st.i2col, P);
+  }
   STARK_TRY(cv.commit(ctx, arena));
-  st.consts_h = boundary_consts(st.roots.g2, st.d.prec, st.d.skips, v.public_wires, v.pfi, v.n_pfi, &st.x_last);
+  st.consts_h = boundary_consts(st.roots.g2, st.d.prec, st.d.skips, v.public_wires, v.pfi, v.n_pfi, !st.pub_cols,
+                                &st.x_last);
   return STARK_OK;
+}
+
+// The column route's coefficients, before anything of the proof is enqueued on s (the interpolation's batch
+// inverse takes a host round trip): I2's into pubc + steps and, with_zb2 (no table gives 1 / Zb2), Zb2's
+// times R^-1 into pubc.
+static stark_status public_coefficients(stark_ctx* ctx, const TraceView& v, const Stage& st, bool with_zb2,
+                                        hipStream_t s) {
+  const uint64_t steps = st.d.steps;
+  const size_t n = v.n_pfi;
+  STARK_HIP(ctx, hipMemsetAsync(st.pubc, 0, 2 * steps * sizeof(fe), s));
+  DomainHint hint;
+  std::vector<uint64_t> staging;
+  hint.log_order = st.d.log_steps;
+  const size_t scratch = lagrange_scratch_elems(n, &hint);  // (n < steps: Z' fits the domain)
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  STARK_TRY(ensure_buf(ctx, ctx->poly, (scratch + 2 * n) * sizeof(fe) + n * sizeof(uint64_t)));
+  fe* mem = (fe*)ctx->poly.ptr;
+  fe* xy = mem + scratch;
+  STARK_TRY(public_points(ctx, st.roots.g2, st.d.skips, st.d.log_steps, v.public_wires, v.pfi, n,
+                          (uint64_t*)(xy + 2 * n), xy, hint, staging, s));
+  fe* z = nullptr;  // (the interpolation synchronises s for its batch inverse: staging is free after it)
+  STARK_TRY(lagrange_interp_device(ctx, xy, xy + n, n, st.pubc + steps, mem, s, &hint, &z));
+  if (with_zb2) {
+    hipLaunchKernelGGL(scale_rinv_kernel, dim3(blocks_for(n + 1)), dim3(256), 0, s, (const fe*)z, (uint64_t)(n + 1),
+                       st.pubc);
+    STARK_HIP(ctx, hipGetLastError());
+  }
+  return buf_release(ctx, ctx->poly, s);
+}
+
+// Column c of pubc (0: Zb2 R^-1, 1: I2) at this host's points.
+static stark_status public_extend(stark_ctx* ctx, const Stage& st, int c, fe* out, hipStream_t s) {
+  return coset_forward(ctx, st.pubc + c * st.d.steps, 1, out, st.d.log_steps, st.d.log_prec, st.d.log_g, st.d.rank,
+                       *st.roots.tw2, *st.roots.twh, s);
 }
 
 // The step columns with zero tails (prove.rs:59-69; inv_best_fft pads the flags), host or device sources
@@ -1357,10 +1488,13 @@ static stark_status a_chain_finish(stark_ctx* ctx, Stage& st, hipStream_t s, hip
 static stark_status zb_enqueue(stark_ctx* ctx, const Stage& st, size_t n_pfi, hipStream_t s, uint64_t* count) {
   const Twiddles* tw2 = st.roots.tw2;
   const uint64_t P = st.d.P;
-  hipLaunchKernelGGL(r1cs_zb_kernel, dim3(blocks_for(P)), dim3(256), 0, s, tw2->d_lo, tw2->d_hi, tw2->kb, P,
-                     (uint64_t)st.d.rank, st.d.log_g, (const fe*)st.consts, (uint32_t)n_pfi, to_dev(st.x_last),
-                     st.mc.rinv, st.mc.one, st.zb, st.sc.izb3 ? nullptr : st.zb + P);
-  STARK_HIP(ctx, hipGetLastError());
+  if (st.pub_cols) STARK_TRY(public_extend(ctx, st, 0, st.zb, s));  // Zb2 from its coefficients
+  if (!st.pub_cols || !st.sc.izb3) {
+    hipLaunchKernelGGL(r1cs_zb_kernel, dim3(blocks_for(P)), dim3(256), 0, s, tw2->d_lo, tw2->d_hi, tw2->kb, P,
+                       (uint64_t)st.d.rank, st.d.log_g, (const fe*)st.consts, (uint32_t)n_pfi, to_dev(st.x_last),
+                       st.mc.rinv, st.mc.one, st.pub_cols ? nullptr : st.zb, st.sc.izb3 ? nullptr : st.zb + P);
+    STARK_HIP(ctx, hipGetLastError());
+  }
   *count = st.sc.izb3 ? P : 2 * P;
   return STARK_OK;
 }
@@ -1387,6 +1521,11 @@ static stark_status constraint_args(stark_ctx* ctx, const TraceView& v, const fe
   ca.inv_zb3 = st.sc.izb3 ? st.sc.izb3 : ca.inv_zb + P;
   ca.interp2 = st.consts + v.n_pfi;
   ca.interp3 = st.consts + 2 * v.n_pfi;
+  ca.i2_col = nullptr;
+  if (st.pub_cols) {  // I2 from its coefficients
+    STARK_TRY(public_extend(ctx, st, 1, st.i2col, s));
+    ca.i2_col = st.i2col;
+  }
   ca.lo = tw2->d_lo;
   ca.hi = tw2->d_hi;
   ca.rows = st.rows;
@@ -1457,6 +1596,7 @@ static stark_status prove_r1cs(stark_ctx* ctx, const TraceView& v, const fe* pre
     memcpy(pin + kPinned4ConstsOff, h.data(), h.size() * sizeof(fe));
     STARK_HIP(ctx, hipMemcpyAsync(st.consts, pin + kPinned4ConstsOff, h.size() * sizeof(fe), hipMemcpyHostToDevice, s));
   }
+  if (st.pub_cols) STARK_TRY(public_coefficients(ctx, v, st, !pre && !st.ca.tinv, s));
   if (v.dev_pack && !pre) STARK_TRY(stage_pack(ctx, v, st, s));
   else STARK_TRY(stage_uploads(ctx, v, pre, st, s));
   clk.mark("setup + uploads enqueued");
@@ -1647,8 +1787,10 @@ stark_status circuit_lde(stark_ctx* ctx, const fe* coef, const uint8_t* flag_byt
   const Twiddles *tw2 = roots.tw2, *tw1i = roots.tw1i, *twh = roots.twh;
   for (size_t i = 0; i < n_pfi; ++i)
     if (public_first_indices[2 * i + 1] >= steps) return STARK_ERR_BAD_ARG;
-  DevBuf& tmp = ctx->lde_tmp;  // 6 step columns, then Zb2 / Zb3 and the x_k (2 P + n_pfi)
-  STARK_TRY(ensure_buf(ctx, tmp, (6 * steps + 2 * P + n_pfi + 1) * sizeof(fe)));
+  // The column route: Zb2 from its coefficients (public_zb2_coefficients), as the proofs take I2.
+  const bool zb2_col = with_zb && public_columns(ctx, n_pfi, steps);
+  DevBuf& tmp = ctx->lde_tmp;  // 6 step columns, then Zb2 / Zb3, the x_k (2 P + n_pfi) and Zb2's coefficients
+  STARK_TRY(ensure_buf(ctx, tmp, (6 * steps + 2 * P + n_pfi + 1 + (zb2_col ? steps : 0)) * sizeof(fe)));
   stark_status st = ensure_buf(ctx, out, (with_zb ? 8 : 6) * P * sizeof(fe));
   if (st == STARK_OK) {
     fe* raw = (fe*)tmp.ptr;
@@ -1733,17 +1875,24 @@ stark_status circuit_lde(stark_ctx* ctx, const fe* coef, const uint8_t* flag_byt
     // Zb2 = prod_k (x - x_k), Zb3 = x - x_last (utils.rs:438-474) and their inverses (0 -> 0).
     const uint64_t skips = prec / steps;
     std::vector<fe> xk(n_pfi + 1);
-    for (size_t i = 0; i < n_pfi; ++i) xk[i] = to_dev(F.pow_u64(g2, skips * public_first_indices[2 * i + 1]));
+    std::vector<uint64_t> staging;  // (alive until the synchronisation below)
+    for (size_t i = 0; !zb2_col && i < n_pfi; ++i)
+      xk[i] = to_dev(F.pow_u64(g2, skips * public_first_indices[2 * i + 1]));
     fe* zb = raw + 6 * steps;
     fe* d_xk = zb + 2 * P;
     const Mont mc = mont();
-    if (st == STARK_OK && with_zb && n_pfi &&
+    if (st == STARK_OK && with_zb && !zb2_col && n_pfi &&
         hipMemcpyAsync(d_xk, xk.data(), n_pfi * sizeof(fe), hipMemcpyHostToDevice, s) != hipSuccess)
       st = STARK_ERR_HIP;
+    if (st == STARK_OK && zb2_col) {
+      fe* zc = d_xk + n_pfi + 1;
+      st = public_zb2_coefficients(ctx, g2, skips, log_steps, public_first_indices, n_pfi, zc, staging, s);
+      if (st == STARK_OK) st = coset_forward(ctx, zc, 1, zb, log_steps, log_prec, log_g, rank, *tw2, *twh, s);
+    }
     if (st == STARK_OK && with_zb) {
       hipLaunchKernelGGL(r1cs_zb_kernel, dim3(blocks_for(P)), dim3(256), 0, s, tw2->d_lo, tw2->d_hi, tw2->kb, P,
                          (uint64_t)rank, log_g, (const fe*)d_xk, (uint32_t)n_pfi,
-                         to_dev(F.pow_u64(g2, prec - skips)), mc.rinv, mc.one, zb, zb + P);
+                         to_dev(F.pow_u64(g2, prec - skips)), mc.rinv, mc.one, zb2_col ? nullptr : zb, zb + P);
       st = multi_inv_device(ctx, zb, (fe*)out.ptr + 6 * P, 2 * P, s);
     }
     if (st == STARK_OK && !verify_only) {  // K, F0-F2 as Montgomery images (ConstraintArgs::mont_cols; the Zb inverses are)
@@ -1951,6 +2100,7 @@ static stark_status dprove_begin(stark_ctx* ctx, uint32_t world, uint32_t rank, 
   d.d_tr = st.d_tr;
   STARK_HIP(ctx, hipMemcpyAsync(st.consts, st.consts_h.data(), st.consts_h.size() * sizeof(fe), hipMemcpyHostToDevice,
                                 s));
+  if (st.pub_cols) STARK_TRY(public_coefficients(ctx, v, st, !pre && !st.ca.tinv, s));
   STARK_TRY(stage_uploads(ctx, v, pre, st, s));
   STARK_TRY(stark_merkle_new(ctx, &d.acc_tree));
   STARK_TRY(stage_accumulator(ctx, st, d.acc_tree, nullptr, s));  // on every rank

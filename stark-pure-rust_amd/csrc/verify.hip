@@ -837,7 +837,24 @@ static stark_status verify_r1cs(stark_ctx* ctx, const PreparedCircuit& c, const 
     bx.push_back(F.pow_u64(g2, skips * c.pfi[i + 1]));
     by.push_back(pub[c.pfi[i]]);
   }
-  const std::vector<HostFp> interp2 = lagrange_interp(bx, by);
+  // (from the context's threshold on, by the subproduct tree on the GPU: x_k = g1^(w_k), g1 = g2^skips)
+  std::vector<HostFp> interp2;
+  const size_t n_b = bx.size(), col_min = ctx->public_column_min ? ctx->public_column_min : kDefaultVerifyColumnMin;
+  if (n_b > 0 && n_b >= col_min && n_b < steps) {
+    std::vector<uint64_t> exps(n_b), ys(4 * n_b), out(4 * n_b), g1c(4);
+    for (size_t i = 0; i < n_b; ++i) {
+      exps[i] = c.pfi[2 * i + 1];
+      F.to_canonical(by[i], &ys[4 * i]);
+    }
+    F.to_canonical(F.pow_u64(g2, skips), g1c.data());
+    uint32_t log_order = 0;
+    while (((uint64_t)1 << log_order) < steps) ++log_order;
+    STARK_TRY(stark_lagrange_interp_domain(ctx, g1c.data(), log_order, exps.data(), ys.data(), n_b, out.data()));
+    interp2.resize(n_b);
+    for (size_t i = 0; i < n_b; ++i) interp2[i] = F.from_canonical(&out[4 * i]);
+  } else {
+    interp2 = lagrange_interp(bx, by);
+  }
   const HostFp x_last = F.pow_u64(g2, (steps - 1) * skips);
   const std::vector<HostFp> interp3 = lagrange_interp({x_last}, {F.one()});
   // r (utils.rs:272-290) and k (verify.rs:164-173).

@@ -3,8 +3,8 @@
 Names, argument meaning and error behaviour follow the Rust items the C ABI
 replaces (see include/stark_hip.h for file:line citations):
 
-    fri::fft::{best_fft, inv_best_fft, expand_root_of_unity, serial_fft}
-    fri::poly_utils::{multi_inv, eval_poly_at}
+    fri::fft::{best_fft, inv_best_fft, expand_root_of_unity, serial_fft, mul_polys, div_polys}
+    fri::poly_utils::{multi_inv, eval_poly_at, zpoly, lagrange_interp}
     fri::utils::{blake, get_pseudorandom_indices}
     commitment::merkle_proof_in_place::MerkleProofInPlace (MerkleTree trait)
     commitment::merkle_tree::{Proof, verify_multi_branch}
@@ -54,6 +54,7 @@ _SIGNATURES = {
     "stark_ctx_last_error": ([_vp], ctypes.c_char_p),
     "stark_ctx_stream": ([_vp], _vp),
     "stark_ctx_set_cache_limit": ([_vp, ctypes.c_size_t], ctypes.c_int),
+    "stark_ctx_set_public_column_min": ([_vp, ctypes.c_size_t], ctypes.c_int),
     "stark_ctx_memory": ([_vp, _szp, _szp, _szp], ctypes.c_int),
     "stark_best_fft": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p], ctypes.c_int),
     "stark_inv_best_fft": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p], ctypes.c_int),
@@ -63,6 +64,14 @@ _SIGNATURES = {
     "stark_expand_root_of_unity": ([_vp, _u64p, _u64p, ctypes.c_size_t, _szp], ctypes.c_int),
     "stark_multi_inv": ([_vp, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
     "stark_eval_poly_at_multi": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
+    "stark_zpoly": ([_vp, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
+    "stark_lagrange_interp": ([_vp, _u64p, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
+    "stark_lagrange_interp_domain": ([_vp, _u64p, ctypes.c_uint32, _u64p, _u64p, ctypes.c_size_t, _u64p],
+                                     ctypes.c_int),
+    "stark_mul_polys": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p],
+                        ctypes.c_int),
+    "stark_div_polys": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p],
+                        ctypes.c_int),
     "stark_blake": ([_u8p, ctypes.c_size_t, _u8p], None),
     "stark_get_pseudorandom_indices": ([_u8p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_uint32,
                                         ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
@@ -304,6 +313,13 @@ class Context:
         """Cap on the context's cached tables (full last-pass twiddle tables, IDX extensions)."""
         self.check(self.lib.stark_ctx_set_cache_limit(self.h, int(nbytes)), "set_cache_limit")
 
+    PUBLIC_COLUMN_NEVER = ctypes.c_size_t(-1).value  # SIZE_MAX
+
+    def set_public_column_min(self, m: int):
+        """From how many public points proofs and verifications take the column route (I2 and Zb2 extended
+        from their coefficients); 0 = the default, PUBLIC_COLUMN_NEVER = never.  Same proofs either way."""
+        self.check(self.lib.stark_ctx_set_public_column_min(self.h, int(m)), "set_public_column_min")
+
     def memory(self) -> dict:
         """{'cached': bytes of cached tables, 'cache_limit': their cap, 'resident': all device bytes held}."""
         c, l, r = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
@@ -416,6 +432,46 @@ class Context:
         out = np.empty_like(x)
         self.check(self.lib.stark_eval_poly_at_multi(self.h, _p64(p), len(p), _p64(x), len(x), _p64(out)),
                    "eval_poly_at")
+        return out
+
+    def zpoly(self, xs) -> np.ndarray:
+        """poly_utils.rs:362-373: the len(xs) + 1 coefficients of prod (X - x), low degree first."""
+        x = _elems(xs)
+        out = np.empty((len(x) + 1, 4), dtype=np.uint64)
+        self.check(self.lib.stark_zpoly(self.h, _p64(x), len(x), _p64(out)), "zpoly")
+        return out
+
+    def lagrange_interp(self, xs, ys, root_of_unity=None, log_order_of_root: int = 0) -> np.ndarray:
+        """poly_utils.rs:409-439: the len(xs) coefficients of the interpolant, low degree first.  With
+        root_of_unity, `xs` is a list of exponents and the points are root_of_unity^xs[i] (the prover's
+        boundary points): same result, denominators by one transform of that order."""
+        y = _elems(ys)
+        out = np.empty_like(y)
+        if root_of_unity is None:
+            x = _elems(xs)
+            if len(x) != len(y):
+                raise ValueError("lagrange_interp: one y per x")
+            self.check(self.lib.stark_lagrange_interp(self.h, _p64(x), _p64(y), len(y), _p64(out)), "lagrange_interp")
+            return out
+        e = np.ascontiguousarray(xs, dtype=np.uint64).reshape(-1)
+        if len(e) != len(y):
+            raise ValueError("lagrange_interp: one y per exponent")
+        self.check(self.lib.stark_lagrange_interp_domain(self.h, _p64(_limbs(root_of_unity)), log_order_of_root,
+                                                         _p64(e), _p64(y), len(y), _p64(out)), "lagrange_interp")
+        return out
+
+    def mul_polys(self, a, b, root_of_unity, log_order_of_root: int) -> np.ndarray:
+        """fft.rs:381-395: the cyclic product of length 2^log_order_of_root."""
+        return self._mul_div(self.lib.stark_mul_polys, "mul_polys", a, b, root_of_unity, log_order_of_root)
+
+    def div_polys(self, a, b, root_of_unity, log_order_of_root: int) -> np.ndarray:
+        """fft.rs:419-432."""
+        return self._mul_div(self.lib.stark_div_polys, "div_polys", a, b, root_of_unity, log_order_of_root)
+
+    def _mul_div(self, fn, where, a, b, root, log_n) -> np.ndarray:
+        a, b = _elems(a), _elems(b)
+        out = np.empty((1 << log_n, 4), dtype=np.uint64)
+        self.check(fn(self.h, _p64(a), len(a), _p64(b), len(b), _p64(_limbs(root)), log_n, _p64(out)), where)
         return out
 
     def multi_interp_4(self, xsets, ysets) -> np.ndarray:
