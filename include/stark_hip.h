@@ -38,8 +38,9 @@ extern "C" {
  * 3: device groups, stark_group_* (round 6).
  * 4: stark_group_prove_low_degree(_dev), stark_class_deal_dev / stark_class_merge_dev.
  * 5: stark_zpoly, stark_lagrange_interp(_domain), stark_mul_polys / stark_div_polys,
- *    stark_ctx_set_public_column_min. */
-#define STARK_ABI_VERSION 5u
+ *    stark_ctx_set_public_column_min.
+ * 6: stark_eval_poly_multipoint(_dev), stark_ctx_set_multipoint_tree_min, stark_divrem_polys. */
+#define STARK_ABI_VERSION 6u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -155,9 +156,30 @@ stark_status stark_expand_root_of_unity(stark_ctx* ctx, const uint64_t root[4], 
 /* multi_inv<T>(values) -> Vec<T> (poly_utils.rs:38-70); zero maps to zero. */
 stark_status stark_multi_inv(stark_ctx* ctx, const uint64_t* values, size_t n, uint64_t* out);
 /* xs.map(|x| eval_poly_at(poly, x)) (poly_utils.rs:93-102 as used at
- * r1cs-stark/src/prove.rs:216-220): out[i] = sum_k poly[k] * xs[i]^k. */
+ * r1cs-stark/src/prove.rs:216-220): out[i] = sum_k poly[k] * xs[i]^k.
+ * This is the library's first evaluation kernel, one thread per point with a serial Horner chain, kept exactly
+ * as it is: the tests use it as the independent check of the tree routines below.  A caller with a long
+ * polynomial or many points takes stark_eval_poly_multipoint, which gives the same values. */
 stark_status stark_eval_poly_at_multi(stark_ctx* ctx, const uint64_t* poly, size_t deg_plus_1,
                                       const uint64_t* xs, size_t n, uint64_t* out);
+/* The same values (eval_poly_at, poly_utils.rs:93-102, over every x; the verifier's pattern at
+ * r1cs-stark/src/verify.rs:202-205 is few points against a polynomial of `steps` coefficients) by one of two
+ * routes.  Split Horner: a group of up to 256 lanes per (coefficient chunk, point), Horner in x^G per lane,
+ * partial sums added by further launches.  Subproduct tree: the tree of stark_zpoly over xs, one power-series reciprocal and
+ * the descent of the tree, O((n + deg) log^2) products; taken when min(n, deg_plus_1) reaches
+ * the context's threshold (below) and deg_plus_1 + N <= 2^27, N = n padded to a power of two >= 32.
+ * deg_plus_1 = 0 gives zeros; n = 0 is a no-op.  All arithmetic is exact: both routes are bit-identical to
+ * Horner. */
+stark_status stark_eval_poly_multipoint(stark_ctx* ctx, const uint64_t* poly, size_t deg_plus_1,
+                                        const uint64_t* xs, size_t n, uint64_t* out);
+/* Device-resident form: asynchronous on `stream` (NULL = the context stream), no host synchronisation. */
+stark_status stark_eval_poly_multipoint_dev(stark_ctx* ctx, const uint64_t* d_poly, size_t deg_plus_1,
+                                            const uint64_t* d_xs, size_t n, uint64_t* d_out, void* stream);
+/* min(n, deg_plus_1) from which stark_eval_poly_multipoint takes the tree, and the point count from which
+ * stark_lagrange_interp at arbitrary points takes its denominators Z'(x_i) down the tree it has built (no
+ * reference counterpart; the results are the same either way).  0 restores the measured default,
+ * SIZE_MAX means never, 1 means whenever the transform sizes allow. */
+stark_status stark_ctx_set_multipoint_tree_min(stark_ctx* ctx, size_t m);
 /* multi_interp_4<T>(xsets, ysets) -> Vec<[T; 4]> (poly_utils.rs:449-511): for
  * each row the coefficients of the cubic through (xs[k], ys[k]), k < 4; rows
  * x 4 elements in, rows x 4 coefficients out (zero denominators map to zero
@@ -201,6 +223,16 @@ stark_status stark_mul_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const
  * (a zero of it maps to zero). */
 stark_status stark_div_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
                              const uint64_t root[4], uint32_t log_n, uint64_t* out);
+
+/* div_polys<T>(a, b) -> Vec<T> and mod_polys<T>(a, b) -> Vec<T> (poly_utils.rs:235-262, 291-295) in one call:
+ * division with remainder.  b's trailing zero coefficients are dropped, leaving lb' (lb' = 0:
+ * STARK_ERR_BAD_ARG, where the reference underflows; la < lb': STARK_ERR_BAD_LENGTH, its
+ * assert!(a.len() >= b.len())).  q receives la - lb' + 1 coefficients and *q_len that count (a's leading zeros
+ * are not trimmed, as in the reference).  r (may be NULL) receives the first lb - 1 coefficients of a - b q,
+ * lb as given (mod_polys drains b.len() - 1 of them).  By a power-series reciprocal of the reversed divisor and
+ * two transform-size products, O(la log la); la <= 2^27. */
+stark_status stark_divrem_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
+                                uint64_t* q, size_t* q_len, uint64_t* r);
 
 /* ---- Blake2s + index sampler (packages/fri/src/utils.rs) ------------------ */
 /* blake(message) -> Vec<u8> (fri/src/utils.rs:5-10): Blake2s-256, unkeyed. */

@@ -104,6 +104,61 @@ __global__ void eval_poly_kernel(const fe* __restrict__ poly, uint64_t deg1, con
   fe_store(out + i, y);
 }
 
+// Split Horner: the grid is (coefficient chunk, point), flattened.  A group of G = 2^log_g lanes sums chunk c
+// (coefficients [c chunk, min((c + 1) chunk, len))) of point p's polynomial at X = x_p^(2^log_pow):
+//   out[p chunks + c] = sum_k coef[c chunk + k] X^k,
+// lane l taking k = l, l + G, .. (the group's loads are contiguous) by Horner in X^G, scaled by X^l, and the G
+// results summed through LDS (limb-major, as poly.hip's images).  G = 256, the whole workgroup, when the
+// points are few; when the points alone nearly fill the device a group is narrower (256 / G points per
+// workgroup), since a lane's two powers cost up to 2 log2 G products whatever it sums; G = 1 is plain Horner.
+// The partial sums of a point are the coefficients of a polynomial in X^chunk: the next launch reads them
+// with coef_stride = chunks and log_pow raised by log2 chunk (chunk is a power of two), until one chunk is
+// left.  Sums are exact, so their order does not matter.  coef_stride = 0: every point reads the same polynomial.
+constexpr uint32_t kSplitThreads = 256;
+__global__ __launch_bounds__(kSplitThreads) void eval_split_kernel(const fe* __restrict__ coef, uint64_t coef_stride,
+                                                                   uint64_t len, const fe* __restrict__ xs,
+                                                                   uint64_t npts, uint32_t log_pow, uint64_t chunk,
+                                                                   uint32_t chunks, uint32_t log_g,
+                                                                   fe* __restrict__ out, MontConsts mc) {
+  __shared__ uint32_t sum[8 * kSplitThreads];
+  const uint32_t t = threadIdx.x, G = 1u << log_g, l = t & (G - 1);
+  const uint64_t p = (uint64_t)(blockIdx.x / chunks) * (kSplitThreads >> log_g) + (t >> log_g);
+  const uint64_t c = blockIdx.x % chunks, at = c * chunk;
+  const uint64_t clen = len - at < chunk ? len - at : chunk;  // at < len: the grid has ceil(len / chunk) chunks
+  fe y = fe_zero();
+  if (p < npts && l < clen) {
+    const fe* src = coef + p * coef_stride + at;
+    fe sq = fe_mul(fe_load(xs + p), mc.r2);  // Montgomery images from here: X, then X^(2^i)
+    for (uint32_t i = 0; i < log_pow; ++i) sq = fe_mul(sq, sq);
+    fe xl = mc.one;  // X^l
+    for (uint32_t i = 0; i < log_g; ++i) {
+      if ((l >> i) & 1) xl = fe_mul(xl, sq);
+      sq = fe_mul(sq, sq);
+    }
+    // sq = X^G; this lane's coefficients l + G j, last first
+    for (uint64_t k = l + (clen - 1 - l) / G * G;; k -= G) {
+      y = fe_add(fe_mul(y, sq), fe_load(src + k));
+      if (k < G) break;
+    }
+    if (log_g) y = fe_mul(y, xl);
+  }
+#pragma unroll
+  for (int w = 0; w < 8; ++w) sum[w * kSplitThreads + t] = y.w[w];
+  __syncthreads();
+  for (uint32_t off = G / 2; off > 0; off >>= 1) {
+    if (l < off) {
+      fe o;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) o.w[w] = sum[w * kSplitThreads + t + off];
+      y = fe_add(y, o);
+#pragma unroll
+      for (int w = 0; w < 8; ++w) sum[w * kSplitThreads + t] = y.w[w];
+    }
+    __syncthreads();
+  }
+  if (l == 0 && p < npts) fe_store(out + p * chunks + c, y);
+}
+
 // powers[i] = w^i (canonical) for i < count, from the two-level tables.
 __global__ void powers_kernel(const fe* __restrict__ lo, const fe* __restrict__ hi, uint32_t kb, uint64_t count,
                               fe* __restrict__ out) {
@@ -329,6 +384,71 @@ stark_status eval_poly_device(stark_ctx* ctx, const fe* d_poly, uint64_t deg_plu
   hipLaunchKernelGGL(eval_poly_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_poly, deg_plus_1, d_xs, n,
                      d_out, mont_consts());
   STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
+// The split Horner's shape for `pts` polynomials of `len` coefficients: how many ways a point's sum is split,
+// over the 2^log_g lanes of a group first (no further launch) and over chunks beyond 256 lanes.  The split
+// doubles until the launch has 2^19 lanes (eight waves per SIMD of 256 compute units) or a lane would sum fewer
+// than 16 coefficients, which is what its two powers cost at G = 256.  By this count, not by a measurement.
+struct SplitPlan {
+  uint32_t log_g;
+  uint64_t chunk, chunks;  // chunk: a power of two
+};
+static SplitPlan split_plan(uint64_t len, uint64_t pts) {
+  uint64_t split = 1;
+  while (pts * split < ((uint64_t)1 << 19) && split * 32 <= len) split <<= 1;
+  SplitPlan sp{0, 1, 1};
+  while (((uint64_t)2 << sp.log_g) <= split && sp.log_g < 8) ++sp.log_g;
+  const uint64_t want = split >> sp.log_g, per = (len + want - 1) / want;
+  while (sp.chunk < per) sp.chunk <<= 1;
+  sp.chunks = (len + sp.chunk - 1) / sp.chunk;
+  return sp;
+}
+// Points per slice: a slice's partial sums stay at or below 2^22 elements (128 MiB) and one launch's grid with it.
+constexpr uint64_t kSplitSliceElems = (uint64_t)1 << 22;
+static uint64_t split_slice(uint64_t n, uint64_t chunks) {
+  const uint64_t s = kSplitSliceElems / chunks;
+  return s < 1 ? 1 : (s < n ? s : n);
+}
+
+size_t eval_split_scratch_elems(uint64_t deg_plus_1, uint64_t n) {
+  if (deg_plus_1 == 0 || n == 0) return 0;
+  const uint64_t chunks = split_plan(deg_plus_1, n).chunks;
+  return chunks == 1 ? 0 : (size_t)(2 * split_slice(n, chunks) * chunks);
+}
+
+stark_status eval_split_device(stark_ctx* ctx, const fe* d_poly, uint64_t deg_plus_1, const fe* d_xs, uint64_t n,
+                               fe* d_out, fe* mem, hipStream_t s) {
+  if (n == 0) return STARK_OK;
+  if (deg_plus_1 == 0) {
+    STARK_HIP(ctx, hipMemsetAsync(d_out, 0, n * sizeof(fe), s));
+    return STARK_OK;
+  }
+  const MontConsts mc = mont_consts();
+  const SplitPlan first = split_plan(deg_plus_1, n);
+  const uint64_t slice = split_slice(n, first.chunks);
+  fe* bufs[2] = {mem, mem + slice * first.chunks};
+  for (uint64_t p0 = 0; p0 < n; p0 += slice) {
+    const uint64_t pts = n - p0 < slice ? n - p0 : slice;
+    const fe* coef = d_poly;
+    uint64_t stride = 0, len = deg_plus_1;
+    uint32_t log_pow = 0;
+    SplitPlan sp = first;
+    for (int w = 0;; w ^= 1) {
+      fe* dst = sp.chunks == 1 ? d_out + p0 : bufs[w];
+      const uint64_t per_wg = kSplitThreads >> sp.log_g;  // points per workgroup
+      hipLaunchKernelGGL(eval_split_kernel, dim3((unsigned)((pts + per_wg - 1) / per_wg * sp.chunks)),
+                         dim3(kSplitThreads), 0, s, coef, stride, len, d_xs + p0, pts, log_pow, sp.chunk,
+                         (uint32_t)sp.chunks, sp.log_g, dst, mc);
+      STARK_HIP(ctx, hipGetLastError());
+      if (sp.chunks == 1) break;
+      coef = dst;
+      stride = len = sp.chunks;
+      for (uint64_t c = sp.chunk; c >>= 1;) ++log_pow;  // + log2 chunk
+      sp = split_plan(len, pts);
+    }
+  }
   return STARK_OK;
 }
 

@@ -141,6 +141,12 @@ constexpr size_t kDefaultCacheLimit = (size_t)4 << 30;
 // (profiles/public_column_ab.txt).
 constexpr size_t kDefaultPublicColumnMin = 128;
 constexpr size_t kDefaultVerifyColumnMin = 1024;
+// min(points, coefficients) from which stark_eval_poly_multipoint and the unhinted lagrange_interp descend the
+// subproduct tree instead of running the split Horner (stark_ctx_set_multipoint_tree_min): the smallest
+// measured min(n, deg_plus_1) from which the tree beats the split Horner by more than three spreads at every
+// measured shape (at 8,192 x 8,192 the split Horner still wins, 0.78 ms against 1.86;
+// profiles/multipoint_eval_ab.txt).
+constexpr size_t kDefaultMultipointTreeMin = 65536;
 
 }  // namespace stark
 
@@ -193,6 +199,9 @@ struct stark_ctx {
   // Public points from which proofs and verifications take the column route (stark_ctx_set_public_column_min);
   // 0: stark::kDefaultPublicColumnMin.
   size_t public_column_min = 0;
+  // min(points, coefficients) from which multi-point evaluation descends the subproduct tree
+  // (stark_ctx_set_multipoint_tree_min); 0: stark::kDefaultMultipointTreeMin.
+  size_t multipoint_tree_min = 0;
 };
 
 namespace stark {
@@ -267,6 +276,11 @@ stark_status multi_inv_device(stark_ctx* ctx, const fe* d_in, fe* d_out, uint64_
 // out[i] = sum_k poly[k] xs[i]^k on device buffers (Horner, one point per thread; field_ops.hip).
 stark_status eval_poly_device(stark_ctx* ctx, const fe* d_poly, uint64_t deg_plus_1, const fe* d_xs, uint64_t n,
                               fe* d_out, hipStream_t s);
+// The same by the split Horner (field_ops.hip: a group of lanes per (coefficient chunk, point), partial sums added by
+// further launches of the same kernel); mem holds eval_split_scratch_elems(deg_plus_1, n) elements.
+size_t eval_split_scratch_elems(uint64_t deg_plus_1, uint64_t n);
+stark_status eval_split_device(stark_ctx* ctx, const fe* d_poly, uint64_t deg_plus_1, const fe* d_xs, uint64_t n,
+                               fe* d_out, fe* mem, hipStream_t s);
 
 // The subproduct tree of zpoly / lagrange_interp (poly.hip): n points padded to N = 2^log_N, the top's
 // coefficients in z (N), and the transforms of each of the `levels` NTT levels in zt (2 N per level).
@@ -292,6 +306,21 @@ struct DomainHint {
 size_t lagrange_scratch_elems(size_t n, const DomainHint* hint);
 stark_status lagrange_interp_device(stark_ctx* ctx, const fe* d_xs, const fe* d_ys, size_t n, fe* d_out, fe* mem,
                                     hipStream_t s, const DomainHint* hint, fe** z_out);
+// g = 1 / h mod Y^(2^log_k) (canonical, 2^log_k coefficients into d_g; log_k >= 5) for h of hlen coefficients
+// (the rest zero) with h(0) != 0: h0_inv = the Montgomery image of 1 / h(0).  A schoolbook phase in one workgroup
+// up to the tree's leaf size, then Newton steps g <- g (2 - h g) by transforms on tree_twiddles' roots.  mem holds
+// 4 2^log_k elements.
+stark_status poly_recip_device(stark_ctx* ctx, const fe* d_h, size_t hlen, uint32_t log_k, const fe& h0_inv, fe* d_g,
+                               fe* mem, hipStream_t s);
+// f (deg_plus_1 >= 1 coefficients) at the points of a built tree, by the descent of the tree (the transpose of
+// the interpolation's way up): n values into d_out.  d_xs are the points the tree was built from.  mem holds
+// poly_descent_elems(t, deg_plus_1) elements; t.z is overwritten with the leaf level.  Fully asynchronous on s.
+size_t poly_descent_elems(const PolyTree& t, size_t deg_plus_1);
+stark_status poly_tree_eval(stark_ctx* ctx, const PolyTree& t, const fe* d_xs, const fe* d_f, size_t deg_plus_1,
+                            fe* d_out, fe* mem, hipStream_t s);
+// Multi-point evaluation on device buffers by the route stark_eval_poly_multipoint documents (takes ctx->poly).
+stark_status eval_multipoint_device(stark_ctx* ctx, const fe* d_poly, size_t deg_plus_1, const fe* d_xs, size_t n,
+                                    fe* d_out, hipStream_t s);
 // d_xs[i] = root^d_exps[i], canonical (tw = the root's tables).
 stark_status poly_domain_points(stark_ctx* ctx, const Twiddles& tw, const uint64_t* d_exps, size_t n, fe* d_xs,
                                 hipStream_t s);

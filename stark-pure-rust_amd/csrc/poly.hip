@@ -1,5 +1,7 @@
 // Polynomial machinery on the GPU: zpoly and lagrange_interp (packages/fri/src/poly_utils.rs:362-439) by a
-// subproduct tree, and the DFT mul_polys / div_polys (packages/fri/src/fft.rs:381-432).
+// subproduct tree, the DFT mul_polys / div_polys (packages/fri/src/fft.rs:381-432), multi-point evaluation
+// (eval_poly_at, poly_utils.rs:93-102, over many points) down the same tree, and division with remainder
+// (div_polys / mod_polys, poly_utils.rs:235-295) by a power-series reciprocal.
 //
 // The tree.  n points are padded with points x = 0 to N = max(kLeaf, the next power of two): every node of
 // level l is then monic of degree exactly 2^l, stored as its 2^l low coefficients (the leading 1 is
@@ -30,6 +32,9 @@ namespace stark {
 
 constexpr uint32_t kLeafLog = 5, kLeaf = 1u << kLeafLog, kPolyThreads = 256;
 static_assert(kPolyThreads % kLeaf == 0, "a leaf group lies in one workgroup");
+// The descent's largest job: coefficients plus padded points (its product is a transform of up to 2^28 points,
+// tree_twiddles' largest), and the longest dividend of stark_divrem_polys.
+constexpr size_t kMultipointTreeLimit = (size_t)1 << 27;
 
 struct PolyConsts {
   fe r2;    // R^2 mod p: montmul(x, r2) = Montgomery image of canonical x
@@ -191,6 +196,122 @@ __global__ void poly_pointwise_kernel(const fe* __restrict__ a, const fe* __rest
   if (i < n) fe_store(out + i, fe_mul(fe_mul(fe_load(a + i), fe_load(b + i)), r2));
 }
 
+// The schoolbook phase of the reciprocal: g = 1 / h mod Y^kLeaf in one workgroup.  Lane t keeps
+// acc_t = sum_(j >= 1) h_j g_(t - j) over the g known so far; once g_m is out, every later lane adds its
+// h_(t - m) g_m and lane m + 1, whose sum is then complete, makes g_(m + 1) = -acc / h_0.
+__global__ __launch_bounds__(kPolyThreads) void poly_recip_leaf_kernel(const fe* __restrict__ h, uint64_t hlen,
+                                                                       fe h0_inv, PolyConsts pc, fe* __restrict__ g) {
+  __shared__ uint32_t hl[8 * kPolyThreads], gl[8 * kPolyThreads];
+  const uint32_t t = threadIdx.x;
+  fe hm = fe_zero();
+  if (t < kLeaf && t < hlen) hm = fe_mul(fe_load(h + t), pc.r2);
+  lds_put(hl, t, hm);
+  fe acc = fe_zero();
+  fe gm = fe_mul(h0_inv, pc.unit);  // g_0 (lane 0's; the others overwrite theirs)
+  __syncthreads();
+  for (uint32_t m = 0; m < kLeaf; ++m) {
+    if (t == m) {
+      lds_put(gl, 0, gm);
+      fe_store(g + m, gm);
+    }
+    __syncthreads();
+    if (t > m && t < kLeaf) {
+      acc = fe_add(acc, fe_mul(lds_get(hl, t - m), lds_get(gl, 0)));
+      if (t == m + 1) gm = fe_mul(fe_sub(fe_zero(), acc), h0_inv);
+    }
+    __syncthreads();
+  }
+}
+
+// dst[i] = -src[i], i < n.
+__global__ void poly_neg_kernel(const fe* __restrict__ src, uint64_t n, fe* __restrict__ dst) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) fe_store(dst + i, fe_sub(fe_zero(), fe_load(src + i)));
+}
+
+// out[i] = f[len - 1 - i] for i < count (count <= len), 0 for count <= i < fill: a reversal, cut and padded.
+__global__ void poly_rev_kernel(const fe* __restrict__ f, uint64_t len, uint64_t count, uint64_t fill,
+                                fe* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < fill) fe_store(out + i, i < count ? fe_load(f + (len - 1 - i)) : fe_zero());
+}
+
+// out[i], i < fill: coefficient i of rev_N(Z_top) = Y^N Z_top(1 / Y): 1, then the top's stored coefficients
+// N - 1 down to 0 (less the wrapped 1 at coefficient 0 when top_fix), then zeros.
+__global__ void poly_rev_top_kernel(const fe* __restrict__ top, uint64_t N, int top_fix, uint64_t fill,
+                                    fe* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= fill) return;
+  fe v = fe_zero();
+  if (i == 0) {
+    v.w[0] = 1;
+  } else if (i <= N) {
+    v = fe_load(top + (N - i));
+    if (top_fix && i == N) {
+      fe one = fe_zero();
+      one.w[0] = 1;
+      v = fe_sub(v, one);
+    }
+  }
+  fe_store(out + i, v);
+}
+
+// The root vector: out[i] = F[i + 1] = coefficient i + 1 - N + d of prod, 0 where that index is negative (i < N).
+__global__ void poly_root_vec_kernel(const fe* __restrict__ prod, uint64_t N, uint64_t d, fe* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) fe_store(out + i, i + 1 + d >= N ? fe_load(prod + (i + 1 + d - N)) : fe_zero());
+}
+
+// One level down: child c of parent c / 2 (transforms of m = 2^log_m points, total = children m):
+// out[c][i] = F^[c / 2][i] Z_sibling^[(-i) mod m], the sibling's kept transform completed by Adj (-i has i's parity).
+__global__ void poly_down_mul_kernel(const fe* __restrict__ ft, const fe* __restrict__ zt, uint32_t log_m,
+                                     uint64_t total, Adj adj, fe r2, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t mask = ((uint64_t)1 << log_m) - 1, c = g >> log_m, i = g & mask;
+  const fe z = fe_add(fe_load(zt + ((c ^ 1) << log_m) + ((0 - i) & mask)), (i & 1) ? adj.odd : adj.even);
+  fe_store(out + g, fe_mul(fe_mul(fe_load(ft + ((c >> 1) << log_m) + i), z), r2));
+}
+
+// The kept halves into the next level's layout: out[c][k] = in[c][k], k < m / 2 (in: transforms of m = 2^log_m).
+__global__ void poly_compact_kernel(const fe* __restrict__ in, uint32_t log_m, uint64_t total, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t c = g >> (log_m - 1), k = g & (((uint64_t)1 << (log_m - 1)) - 1);
+  fe_store(out + g, fe_load(in + (c << log_m) + k));
+}
+
+// The leaves of the descent: lane i of a group of kLeaf points, the group's Z_v (coefficients z, the leaf
+// level) and vector F_v in LDS: f(x_i) = sum_j q_j F_v[j] over q = Z_v / (X - x_i) by synthetic division,
+// q_(kLeaf - 1) = 1, q_(j - 1) = z_j + x_i q_j.  Values at the padded points (from n on) are dropped.
+__global__ __launch_bounds__(kPolyThreads) void poly_leaf_eval_kernel(const fe* __restrict__ xs, uint64_t n, uint64_t N,
+                                                                      const fe* __restrict__ z,
+                                                                      const fe* __restrict__ fv, fe r2,
+                                                                      fe* __restrict__ out) {
+  __shared__ uint32_t zl[8 * kPolyThreads], fl[8 * kPolyThreads];
+  const uint32_t t = threadIdx.x, base = t - (t & (kLeaf - 1));
+  const uint64_t g = (uint64_t)blockIdx.x * kPolyThreads + t;
+  lds_put(zl, t, g < N ? fe_load(z + g) : fe_zero());
+  lds_put(fl, t, g < N ? fe_mul(fe_load(fv + g), r2) : fe_zero());  // Montgomery images
+  __syncthreads();
+  if (g >= n) return;
+  const fe x = fe_mul(fe_load(xs + g), r2);
+  fe q = fe_zero(), acc = fe_zero();
+  q.w[0] = 1;
+  for (uint32_t j = kLeaf; j-- > 0;) {
+    if (j + 1 < kLeaf) q = fe_add(lds_get(zl, base + j + 1), fe_mul(q, x));
+    acc = fe_add(acc, fe_mul(q, lds_get(fl, base + j)));
+  }
+  fe_store(out + g, acc);
+}
+
+// r[i] = a[i] - prod[i] for i < m, 0 for m <= i < fill.
+__global__ void poly_sub_kernel(const fe* __restrict__ a, const fe* __restrict__ prod, uint64_t m, uint64_t fill,
+                                fe* __restrict__ r) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < fill) fe_store(r + i, i < m ? fe_sub(fe_load(a + i), fe_load(prod + i)) : fe_zero());
+}
+
 static unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
 // 7^((p - 1) / 2^k): the primitive 2^k-th root the tree's transforms use (the prover's g2, prove.rs:71-82),
@@ -261,8 +382,9 @@ size_t lagrange_scratch_elems(size_t n, const DomainHint* hint) {
   poly_tree_plan(n, t);
   size_t dz = n;
   if (hint && n <= ((size_t)1 << hint->log_order)) dz = (size_t)1 << hint->log_order;
-  // the tree, N's coefficients and transforms, Z (n + 1), Z', den, 1 / den
-  return poly_tree_elems(t) + 3 * t.N + (n + 1) + dz + 2 * n;
+  // the tree, N's coefficients and transforms, Z (n + 1), Z', den, 1 / den; for arbitrary points the descent's
+  // working set (whether it runs is the context's choice, stark_ctx_set_multipoint_tree_min)
+  return poly_tree_elems(t) + 3 * t.N + (n + 1) + dz + 2 * n + (dz == n && n ? poly_descent_elems(t, n) : 0);
 }
 
 stark_status lagrange_interp_device(stark_ctx* ctx, const fe* d_xs, const fe* d_ys, size_t n, fe* d_out, fe* mem,
@@ -291,6 +413,10 @@ stark_status lagrange_interp_device(stark_ctx* ctx, const fe* d_xs, const fe* d_
     hipLaunchKernelGGL(poly_gather_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const fe*)dz, hint->d_exps,
                        (uint64_t)n, den);
     STARK_HIP(ctx, hipGetLastError());
+  } else if (n >= (ctx->multipoint_tree_min ? ctx->multipoint_tree_min : kDefaultMultipointTreeMin) &&
+             n + t.N <= kMultipointTreeLimit) {
+    // arbitrary points, many: Z' down the tree just built (t.z becomes the leaf level, as it does below anyway)
+    STARK_TRY(poly_tree_eval(ctx, t, d_xs, dz, n, den, inv + n, s));
   } else {
     STARK_TRY(eval_poly_device(ctx, dz, n, d_xs, n, den, s));
   }
@@ -325,6 +451,144 @@ stark_status poly_domain_points(stark_ctx* ctx, const Twiddles& tw, const uint64
                      (uint64_t)n, poly_consts().unit, d_xs);
   STARK_HIP(ctx, hipGetLastError());
   return STARK_OK;
+}
+
+// a <- the 2^(log_k + 1) coefficients of a b, for a and b of 2^log_k coefficients each (no wrap); ta and tb
+// hold 2^(log_k + 1) elements each, the product lands in ta.
+static stark_status poly_full_product(stark_ctx* ctx, const fe* a, const fe* b, uint32_t log_k, fe* ta, fe* tb,
+                                      hipStream_t s) {
+  const Twiddles *fwd, *inv;
+  STARK_TRY(tree_twiddles(ctx, log_k + 1, &fwd, &inv));
+  const uint64_t m = (uint64_t)2 << log_k;
+  STARK_TRY(ntt_device_from(ctx, a, 1, ta, log_k + 1, 1, *fwd, false, s));
+  STARK_TRY(ntt_device_from(ctx, b, 1, tb, log_k + 1, 1, *fwd, false, s));
+  hipLaunchKernelGGL(poly_pointwise_kernel, dim3(grid_for(m)), dim3(256), 0, s, (const fe*)ta, (const fe*)tb, m,
+                     poly_consts().r2, ta);
+  STARK_HIP(ctx, hipGetLastError());
+  return ntt_device(ctx, ta, log_k + 1, 1, *inv, true, s);
+}
+
+// Newton's iteration for the power-series reciprocal.  With g = 1 / h mod Y^j, e = h g mod Y^2j is 1 + Y^j e_hi,
+// and g (2 - h g) = g - Y^j (g e_hi) mod Y^2j: the step appends -(g e_hi mod Y^j) to g.  Both products run as
+// cyclic transforms of 2j points: h g has 3j coefficients, whose top j wrap onto the low j, which are known
+// (1, 0, ..) and not read; g e_hi has 2j and does not wrap.  Five transforms of 2j points per step.
+stark_status poly_recip_device(stark_ctx* ctx, const fe* d_h, size_t hlen, uint32_t log_k, const fe& h0_inv, fe* d_g,
+                               fe* mem, hipStream_t s) {
+  if (log_k < kLeafLog || log_k > 27) return STARK_ERR_BAD_LENGTH;
+  const size_t K = (size_t)1 << log_k, hc = hlen < K ? hlen : K;
+  const PolyConsts pc = poly_consts();
+  fe *H = mem, *A = H + K, *B = A + K, *C = B + K;  // h padded; h^ then e; g^; e_hi^ then g e_hi
+  STARK_HIP(ctx, hipMemcpyAsync(H, d_h, hc * sizeof(fe), hipMemcpyDeviceToDevice, s));
+  if (hc < K) STARK_HIP(ctx, hipMemsetAsync(H + hc, 0, (K - hc) * sizeof(fe), s));
+  hipLaunchKernelGGL(poly_recip_leaf_kernel, dim3(1), dim3(kPolyThreads), 0, s, (const fe*)H, (uint64_t)K, h0_inv, pc,
+                     d_g);
+  STARK_HIP(ctx, hipGetLastError());
+  for (uint32_t log_j = kLeafLog; log_j < log_k; ++log_j) {
+    const size_t j = (size_t)1 << log_j;
+    const uint32_t log_m = log_j + 1;
+    const Twiddles *fwd, *inv;
+    STARK_TRY(tree_twiddles(ctx, log_m, &fwd, &inv));
+    STARK_HIP(ctx, hipMemcpyAsync(A, H, 2 * j * sizeof(fe), hipMemcpyDeviceToDevice, s));
+    STARK_TRY(ntt_device(ctx, A, log_m, 1, *fwd, false, s));
+    STARK_TRY(ntt_device_from(ctx, d_g, 1, B, log_m, 1, *fwd, false, s));
+    hipLaunchKernelGGL(poly_pointwise_kernel, dim3(grid_for(2 * j)), dim3(256), 0, s, (const fe*)A, (const fe*)B,
+                       (uint64_t)(2 * j), pc.r2, A);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(ntt_device(ctx, A, log_m, 1, *inv, true, s));
+    STARK_TRY(ntt_device_from(ctx, A + j, 1, C, log_m, 1, *fwd, false, s));
+    hipLaunchKernelGGL(poly_pointwise_kernel, dim3(grid_for(2 * j)), dim3(256), 0, s, (const fe*)C, (const fe*)B,
+                       (uint64_t)(2 * j), pc.r2, C);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(ntt_device(ctx, C, log_m, 1, *inv, true, s));
+    hipLaunchKernelGGL(poly_neg_kernel, dim3(grid_for(j)), dim3(256), 0, s, (const fe*)C, (uint64_t)j, d_g + j);
+    STARK_HIP(ctx, hipGetLastError());
+  }
+  return STARK_OK;
+}
+
+static uint32_t recip_log(size_t count) {  // log2 of the reciprocal's length for `count` coefficients
+  uint32_t l = kLeafLog;
+  while (((size_t)1 << l) < count) ++l;
+  return l;
+}
+
+// The descent of the subproduct tree.  With Z_v the monic product over node v's 2m points, the
+// vector F_v[k], k = 1..2m, holds the first 2m coefficients in 1 / X of the fractional part of f / Z_v.
+//   root     f / Z_top = X^(d - N) rev_d(f)(1 / X) / rev_N(Z_top)(1 / X): F[k] is coefficient k - N + d of
+//            rev_d(f) alpha, alpha = 1 / rev_N(Z_top) mod Y^(d + 1) (one reciprocal, one product; any d);
+//   down     f / Z_L = (f / Z_v) Z_R, so child L's F[k] = sum_(j <= m) z^R_j F_v[k + j] for k <= m: a correlation,
+//            as transforms of 2m points c^[i] = F^[i] z^[-i], whose first m entries no index wraps into;
+//   leaves   (f mod Z_v) / (X - x_i) = (f mod Z_v) / Z_v times q, q = Z_v / (X - x_i), and its coefficient of
+//            1 / X is f(x_i) = sum_j q_j F_v[j + 1] (poly_leaf_eval_kernel).
+// No batch inverse, no host round trip.
+size_t poly_descent_elems(const PolyTree& t, size_t deg_plus_1) {
+  return 6 * ((size_t)1 << recip_log(deg_plus_1)) + 3 * t.N;  // alpha, the reciprocal's and product's 5 K, F, its 2 N
+}
+
+stark_status poly_tree_eval(stark_ctx* ctx, const PolyTree& t, const fe* d_xs, const fe* d_f, size_t deg_plus_1,
+                            fe* d_out, fe* mem, hipStream_t s) {
+  if (deg_plus_1 == 0) return STARK_ERR_BAD_ARG;
+  const uint32_t log_k = recip_log(deg_plus_1);
+  if (log_k > 27) return STARK_ERR_BAD_LENGTH;
+  const size_t K = (size_t)1 << log_k, N = t.N;
+  const PolyConsts pc = poly_consts();
+  fe *alpha = mem, *W = alpha + K, *fv = W + 5 * K, *G = fv + N;
+  hipLaunchKernelGGL(poly_rev_top_kernel, dim3(grid_for(K)), dim3(256), 0, s, (const fe*)t.z, (uint64_t)N,
+                     t.levels > 0 ? 1 : 0, (uint64_t)K, W + 4 * K);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(poly_recip_device(ctx, W + 4 * K, K, log_k, to_dev(FieldHost::get().one()), alpha, W, s));
+  hipLaunchKernelGGL(poly_rev_kernel, dim3(grid_for(K)), dim3(256), 0, s, d_f, (uint64_t)deg_plus_1,
+                     (uint64_t)deg_plus_1, (uint64_t)K, W);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(poly_full_product(ctx, W, alpha, log_k, W + K, W + 3 * K, s));
+  hipLaunchKernelGGL(poly_root_vec_kernel, dim3(grid_for(N)), dim3(256), 0, s, (const fe*)(W + K), (uint64_t)N,
+                     (uint64_t)(deg_plus_1 - 1), fv);
+  STARK_HIP(ctx, hipGetLastError());
+  // the leaf level again (the levels above overwrote it; they are taken from their kept transforms)
+  hipLaunchKernelGGL(poly_leaf_kernel<false>, dim3(grid_for(N)), dim3(kPolyThreads), 0, s, d_xs, (const fe*)nullptr,
+                     (const fe*)nullptr, (uint64_t)t.n, (uint64_t)N, pc.r2, t.z, (fe*)nullptr);
+  STARK_HIP(ctx, hipGetLastError());
+  for (uint32_t lv = t.levels; lv-- > 0;) {
+    const uint32_t log_m = kLeafLog + lv + 1;  // the transforms' size: the parents'
+    const uint32_t parents = (uint32_t)(N >> log_m);
+    const Twiddles *fwd, *inv;
+    STARK_TRY(tree_twiddles(ctx, log_m, &fwd, &inv));
+    STARK_TRY(ntt_device(ctx, fv, log_m, parents, *fwd, false, s));
+    hipLaunchKernelGGL(poly_down_mul_kernel, dim3(grid_for(2 * N)), dim3(256), 0, s, (const fe*)fv,
+                       (const fe*)(t.zt + 2 * N * lv), log_m, (uint64_t)(2 * N), level_adj(lv > 0), pc.r2, G);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(ntt_device(ctx, G, log_m, 2 * parents, *inv, true, s));
+    hipLaunchKernelGGL(poly_compact_kernel, dim3(grid_for(N)), dim3(256), 0, s, (const fe*)G, log_m, (uint64_t)N, fv);
+    STARK_HIP(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(poly_leaf_eval_kernel, dim3(grid_for(N)), dim3(kPolyThreads), 0, s, d_xs, (uint64_t)t.n,
+                     (uint64_t)N, (const fe*)t.z, (const fe*)fv, pc.r2, d_out);
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
+stark_status eval_multipoint_device(stark_ctx* ctx, const fe* d_poly, size_t deg_plus_1, const fe* d_xs, size_t n,
+                                    fe* d_out, hipStream_t s) {
+  if (n == 0) return STARK_OK;
+  if (deg_plus_1 == 0) {
+    STARK_HIP(ctx, hipMemsetAsync(d_out, 0, n * sizeof(fe), s));
+    return STARK_OK;
+  }
+  const size_t tree_min = ctx->multipoint_tree_min ? ctx->multipoint_tree_min : kDefaultMultipointTreeMin;
+  PolyTree t;
+  poly_tree_plan(n, t);
+  const bool tree = (n < deg_plus_1 ? n : deg_plus_1) >= tree_min && deg_plus_1 + t.N <= kMultipointTreeLimit;
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  if (tree) {
+    STARK_TRY(ensure_buf(ctx, ctx->poly, (poly_tree_elems(t) + poly_descent_elems(t, deg_plus_1)) * sizeof(fe)));
+    fe* mem = (fe*)ctx->poly.ptr;
+    STARK_TRY(poly_tree_build(ctx, d_xs, t, mem, s));
+    STARK_TRY(poly_tree_eval(ctx, t, d_xs, d_poly, deg_plus_1, d_out, mem + poly_tree_elems(t), s));
+  } else {
+    STARK_TRY(ensure_buf(ctx, ctx->poly, eval_split_scratch_elems(deg_plus_1, n) * sizeof(fe)));
+    STARK_TRY(eval_split_device(ctx, d_poly, deg_plus_1, d_xs, n, d_out, (fe*)ctx->poly.ptr, s));
+  }
+  return buf_release(ctx, ctx->poly, s);
 }
 
 }  // namespace stark
@@ -443,6 +707,100 @@ stark_status stark_lagrange_interp_domain(stark_ctx* ctx, const uint64_t root[4]
                                           const uint64_t* exps, const uint64_t* ys, size_t n, uint64_t* out) {
   if (!ctx || !root || (n && (!exps || !ys || !out))) return STARK_ERR_BAD_ARG;
   return interp_host(ctx, nullptr, root, log_order, exps, ys, n, out);
+}
+
+stark_status stark_eval_poly_multipoint(stark_ctx* ctx, const uint64_t* poly, size_t deg_plus_1, const uint64_t* xs,
+                                        size_t n, uint64_t* out) {
+  if (!ctx || (n && (!xs || !out)) || (deg_plus_1 && !poly)) return STARK_ERR_BAD_ARG;
+  if (n == 0) return STARK_OK;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  STARK_TRY(ensure_buf(ctx, ctx->io, (deg_plus_1 + 2 * n) * sizeof(fe)));
+  fe* d_poly = (fe*)ctx->io.ptr;
+  fe* d_xs = d_poly + deg_plus_1;
+  fe* d_out = d_xs + n;
+  if (deg_plus_1) STARK_HIP(ctx, hipMemcpyAsync(d_poly, poly, deg_plus_1 * sizeof(fe), hipMemcpyHostToDevice, s));
+  STARK_HIP(ctx, hipMemcpyAsync(d_xs, xs, n * sizeof(fe), hipMemcpyHostToDevice, s));
+  STARK_TRY(eval_multipoint_device(ctx, d_poly, deg_plus_1, d_xs, n, d_out, s));
+  STARK_HIP(ctx, hipMemcpyAsync(out, d_out, n * sizeof(fe), hipMemcpyDeviceToHost, s));
+  STARK_HIP(ctx, hipStreamSynchronize(s));
+  return STARK_OK;
+}
+
+stark_status stark_eval_poly_multipoint_dev(stark_ctx* ctx, const uint64_t* d_poly, size_t deg_plus_1,
+                                            const uint64_t* d_xs, size_t n, uint64_t* d_out, void* stream) {
+  if (!ctx || (n && (!d_xs || !d_out)) || (deg_plus_1 && !d_poly)) return STARK_ERR_BAD_ARG;
+  if (n == 0) return STARK_OK;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  return eval_multipoint_device(ctx, (const fe*)d_poly, deg_plus_1, (const fe*)d_xs, n, (fe*)d_out,
+                                pick_stream(ctx, stream));
+}
+
+stark_status stark_ctx_set_multipoint_tree_min(stark_ctx* ctx, size_t m) {
+  if (!ctx) return STARK_ERR_BAD_ARG;
+  ctx->multipoint_tree_min = m;
+  return STARK_OK;
+}
+
+// div_polys and mod_polys (poly_utils.rs:235-295) in one call.  With b' = b less its trailing zeros (lb'
+// coefficients) and nq = la - lb' + 1: rev(q) = rev(a) / rev(b') mod Y^nq (the power-series reciprocal, whose
+// 1 / b'_lead the host takes), then r = a - b q, of which only the coefficients below lb' - 1 can be non-zero
+// and need b and q below that only: one more transform-size product.  Every size takes this route (the
+// reciprocal's schoolbook phase covers the first 32 coefficients); there is no separate small-size kernel.
+stark_status stark_divrem_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,
+                                uint64_t* q, size_t* q_len, uint64_t* r) {
+  if (!ctx || !q || !q_len || (la && !a) || (lb && !b)) return STARK_ERR_BAD_ARG;
+  size_t lbp = lb;
+  while (lbp && !(b[4 * lbp - 4] | b[4 * lbp - 3] | b[4 * lbp - 2] | b[4 * lbp - 1])) --lbp;
+  if (lbp == 0) return STARK_ERR_BAD_ARG;                                // (the reference underflows here)
+  if (la < lbp || la > kMultipointTreeLimit) return STARK_ERR_BAD_LENGTH;  // assert!(a.len() >= b.len())
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const FieldHost& F = FieldHost::get();
+  const size_t nq = la - lbp + 1, m = lbp - 1, lr = lb - 1;
+  const uint32_t log_k = recip_log(nq), log_r = recip_log(m);
+  const size_t K = (size_t)1 << log_k, Kr = (size_t)1 << log_r;
+  // staging: a, b', q, r
+  STARK_TRY(ensure_buf(ctx, ctx->io, (la + lbp + nq + lr + 1) * sizeof(fe)));
+  fe* d_a = (fe*)ctx->io.ptr;
+  fe* d_b = d_a + la;
+  fe* d_q = d_b + lbp;
+  fe* d_r = d_q + nq;
+  STARK_HIP(ctx, hipMemcpyAsync(d_a, a, la * sizeof(fe), hipMemcpyHostToDevice, s));
+  STARK_HIP(ctx, hipMemcpyAsync(d_b, b, lbp * sizeof(fe), hipMemcpyHostToDevice, s));
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  STARK_TRY(ensure_buf(ctx, ctx->poly, 6 * (K > Kr ? K : Kr) * sizeof(fe)));
+  fe* g = (fe*)ctx->poly.ptr;  // 1 / rev(b'), then 5 K of work: the reciprocal's 4 K with rev(b') behind them
+  fe* W = g + K;
+  hipLaunchKernelGGL(poly_rev_kernel, dim3(grid_for(K)), dim3(256), 0, s, (const fe*)d_b, (uint64_t)lbp,
+                     (uint64_t)(lbp < K ? lbp : K), (uint64_t)K, W + 4 * K);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(poly_recip_device(ctx, W + 4 * K, K, log_k, to_dev(F.inv(F.from_canonical(b + 4 * (lbp - 1)))), g, W, s));
+  hipLaunchKernelGGL(poly_rev_kernel, dim3(grid_for(K)), dim3(256), 0, s, (const fe*)d_a, (uint64_t)la, (uint64_t)nq,
+                     (uint64_t)K, W);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(poly_full_product(ctx, W, g, log_k, W + K, W + 3 * K, s));
+  hipLaunchKernelGGL(poly_rev_kernel, dim3(grid_for(nq)), dim3(256), 0, s, (const fe*)(W + K), (uint64_t)nq,
+                     (uint64_t)nq, (uint64_t)nq, d_q);
+  STARK_HIP(ctx, hipGetLastError());
+  if (r && lr) {
+    fe* R = (fe*)ctx->poly.ptr;  // b and q below X^m, padded to Kr each, then their transforms
+    const size_t qc = nq < m ? nq : m;
+    if (m) STARK_HIP(ctx, hipMemcpyAsync(R, d_b, m * sizeof(fe), hipMemcpyDeviceToDevice, s));
+    if (m < Kr) STARK_HIP(ctx, hipMemsetAsync(R + m, 0, (Kr - m) * sizeof(fe), s));
+    if (qc) STARK_HIP(ctx, hipMemcpyAsync(R + Kr, d_q, qc * sizeof(fe), hipMemcpyDeviceToDevice, s));
+    if (qc < Kr) STARK_HIP(ctx, hipMemsetAsync(R + Kr + qc, 0, (Kr - qc) * sizeof(fe), s));
+    STARK_TRY(poly_full_product(ctx, R, R + Kr, log_r, R + 2 * Kr, R + 4 * Kr, s));
+    hipLaunchKernelGGL(poly_sub_kernel, dim3(grid_for(lr)), dim3(256), 0, s, (const fe*)d_a, (const fe*)(R + 2 * Kr),
+                       (uint64_t)m, (uint64_t)lr, d_r);
+    STARK_HIP(ctx, hipGetLastError());
+  }
+  STARK_TRY(buf_release(ctx, ctx->poly, s));
+  STARK_HIP(ctx, hipMemcpyAsync(q, d_q, nq * sizeof(fe), hipMemcpyDeviceToHost, s));
+  if (r && lr) STARK_HIP(ctx, hipMemcpyAsync(r, d_r, lr * sizeof(fe), hipMemcpyDeviceToHost, s));
+  STARK_HIP(ctx, hipStreamSynchronize(s));
+  *q_len = nq;
+  return STARK_OK;
 }
 
 stark_status stark_mul_polys(stark_ctx* ctx, const uint64_t* a, size_t la, const uint64_t* b, size_t lb,

@@ -64,6 +64,10 @@ _SIGNATURES = {
     "stark_expand_root_of_unity": ([_vp, _u64p, _u64p, ctypes.c_size_t, _szp], ctypes.c_int),
     "stark_multi_inv": ([_vp, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
     "stark_eval_poly_at_multi": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
+    "stark_eval_poly_multipoint": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
+    "stark_eval_poly_multipoint_dev": ([_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp], ctypes.c_int),
+    "stark_ctx_set_multipoint_tree_min": ([_vp, ctypes.c_size_t], ctypes.c_int),
+    "stark_divrem_polys": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, _szp, _u64p], ctypes.c_int),
     "stark_zpoly": ([_vp, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
     "stark_lagrange_interp": ([_vp, _u64p, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
     "stark_lagrange_interp_domain": ([_vp, _u64p, ctypes.c_uint32, _u64p, _u64p, ctypes.c_size_t, _u64p],
@@ -433,6 +437,41 @@ class Context:
         self.check(self.lib.stark_eval_poly_at_multi(self.h, _p64(p), len(p), _p64(x), len(x), _p64(out)),
                    "eval_poly_at")
         return out
+
+    MULTIPOINT_TREE_NEVER = ctypes.c_size_t(-1).value  # SIZE_MAX
+
+    def set_multipoint_tree_min(self, m: int):
+        """min(points, coefficients) from which eval_poly_multipoint (and lagrange_interp at arbitrary points)
+        descends the subproduct tree; 0 = the default, MULTIPOINT_TREE_NEVER = never, 1 = whenever the sizes
+        allow.  Same values either way."""
+        self.check(self.lib.stark_ctx_set_multipoint_tree_min(self.h, int(m)), "set_multipoint_tree_min")
+
+    def eval_poly_multipoint(self, poly, xs) -> np.ndarray:
+        """[eval_poly_at(poly, x) for x in xs] (poly_utils.rs:93-102) by the split Horner or the subproduct
+        tree: eval_poly_at_multi's values for long polynomials and many points."""
+        p = _elems(poly)
+        x = _elems(xs)
+        out = np.empty_like(x)
+        self.check(self.lib.stark_eval_poly_multipoint(self.h, _p64(p), len(p), _p64(x), len(x), _p64(out)),
+                   "eval_poly_multipoint")
+        return out
+
+    def eval_poly_multipoint_dev(self, d_poly: int, deg_plus_1: int, d_xs: int, n: int, d_out: int,
+                                 stream: int = 0) -> None:
+        """The same on device buffers, asynchronous on `stream` (0 = the context's)."""
+        self.check(self.lib.stark_eval_poly_multipoint_dev(self.h, d_poly, deg_plus_1, d_xs, n, d_out,
+                                                           stream or None), "eval_poly_multipoint_dev")
+
+    def divrem_polys(self, a, b):
+        """div_polys and mod_polys (poly_utils.rs:235-295) in one call: (q, r) with a = b q + r, q of
+        len(a) - len(b') + 1 coefficients (b' = b less its trailing zeros), r of len(b) - 1."""
+        a, b = _elems(a), _elems(b)
+        q = np.empty((max(len(a), 1), 4), dtype=np.uint64)
+        r = np.empty((max(len(b), 1) - 1, 4), dtype=np.uint64)
+        nq = ctypes.c_size_t(0)
+        self.check(self.lib.stark_divrem_polys(self.h, _p64(a), len(a), _p64(b), len(b), _p64(q), ctypes.byref(nq),
+                                               _p64(r)), "divrem_polys")
+        return q[:nq.value].copy(), r
 
     def zpoly(self, xs) -> np.ndarray:
         """poly_utils.rs:362-373: the len(xs) + 1 coefficients of prod (X - x), low degree first."""
