@@ -39,8 +39,9 @@ extern "C" {
  * 4: stark_group_prove_low_degree(_dev), stark_class_deal_dev / stark_class_merge_dev.
  * 5: stark_zpoly, stark_lagrange_interp(_domain), stark_mul_polys / stark_div_polys,
  *    stark_ctx_set_public_column_min.
- * 6: stark_eval_poly_multipoint(_dev), stark_ctx_set_multipoint_tree_min, stark_divrem_polys. */
-#define STARK_ABI_VERSION 6u
+ * 6: stark_eval_poly_multipoint(_dev), stark_ctx_set_multipoint_tree_min, stark_divrem_polys.
+ * 7: stark_merkle_forest_*, stark_prove_low_degree_batch(_dev). */
+#define STARK_ABI_VERSION 7u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -271,6 +272,26 @@ stark_status stark_merkle_get_root(const stark_merkle_tree* tree, uint8_t root[3
  * k == 0.  Sets the root returned by get_root. */
 stark_status stark_merkle_gen_proofs(stark_merkle_tree* tree, const size_t* indices, size_t k,
                                      uint8_t* leaves_out, uint8_t* nodes_out);
+/* A forest: `batch` MerkleProofInPlace trees (merkle_proof_in_place.rs:9-50) of n leaves each, built
+ * together by one set of launches; root b and every path of tree b equal what a stark_merkle_tree over
+ * tree b's leaves gives.  1 <= batch <= 65535 (more is STARK_ERR_BAD_ARG). */
+typedef struct stark_merkle_forest stark_merkle_forest;
+/* MerkleProofInPlace::new (merkle_proof_in_place.rs:16-25), for every tree of the forest */
+stark_status stark_merkle_forest_new(stark_ctx* ctx, stark_merkle_forest** out);
+void stark_merkle_forest_free(stark_merkle_forest* forest);
+/* update(leaves) (merkle_proof_in_place.rs:37-42) of every tree: tree b's n leaves of leaf_len bytes
+ * are at leaves + b*n*leaf_len.  n must be a power of two. */
+stark_status stark_merkle_forest_update(stark_merkle_forest* forest, const uint8_t* leaves, size_t n,
+                                        size_t leaf_len, uint32_t batch);
+/* Same, leaves already in device memory; asynchronous on `stream` (NULL = the context stream). */
+stark_status stark_merkle_forest_update_dev(stark_merkle_forest* forest, const uint8_t* d_leaves, size_t n,
+                                            size_t leaf_len, uint32_t batch, void* stream);
+/* get_root() (merkle_tree.rs:66) of every tree: root b to roots + 32*b.  STARK_ERR_STATE before an update. */
+stark_status stark_merkle_forest_roots(stark_merkle_forest* forest, uint8_t* roots /* batch x 32 */);
+/* gen_proofs(indices) (merkle_tree.rs:72, merkle_proof_in_place.rs:44-49) of tree `tree`: outputs as
+ * stark_merkle_gen_proofs'. */
+stark_status stark_merkle_forest_gen_proofs(stark_merkle_forest* forest, uint32_t tree, const size_t* indices,
+                                            size_t k, uint8_t* leaves_out, uint8_t* nodes_out);
 /* verify_multi_branch / Proof::validate (merkle_tree.rs:25-58), host side:
  * returns STARK_OK when every path hashes to root. */
 stark_status stark_merkle_verify(const uint8_t root[32], const size_t* indices, size_t k,
@@ -287,6 +308,18 @@ stark_status stark_prove_low_degree(stark_ctx* ctx, const uint64_t* values, size
 stark_status stark_prove_low_degree_dev(stark_ctx* ctx, const uint64_t* d_values, size_t n,
                                         const uint64_t root[4], size_t max_deg_plus_1,
                                         uint32_t exclude_multiples_of, stark_fri_proof** out);
+/* prove_low_degree (fri.rs:46-224) for `batch` vectors of n values, vector b at values + 4*n*b u64:
+ * out[b] is the proof stark_prove_low_degree returns for vector b, byte for byte.  The batch shares one
+ * chain of launches and one synchronisation.  Arguments are checked as the single call checks them;
+ * batch = 0 is STARK_OK and writes nothing, batch > 65535 is STARK_ERR_BAD_ARG.  On any failure every
+ * out[b] is NULL.  Each handle is freed with stark_fri_proof_free. */
+stark_status stark_prove_low_degree_batch(stark_ctx* ctx, const uint64_t* values, size_t n, uint32_t batch,
+                                          const uint64_t root[4], size_t max_deg_plus_1,
+                                          uint32_t exclude_multiples_of, stark_fri_proof** out /* batch handles */);
+/* Same with values already in device memory (not modified). */
+stark_status stark_prove_low_degree_batch_dev(stark_ctx* ctx, const uint64_t* d_values, size_t n, uint32_t batch,
+                                              const uint64_t root[4], size_t max_deg_plus_1,
+                                              uint32_t exclude_multiples_of, stark_fri_proof** out);
 void stark_fri_proof_free(stark_fri_proof* proof);
 /* serde_json (compact) encoding of Vec<FriProof<BlakeDigest>> (fri.rs:16-26).
  * Writes up to cap bytes (NUL-terminated if room) and the full length to *len. */

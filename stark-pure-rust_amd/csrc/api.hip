@@ -318,6 +318,8 @@ void stark_ctx_destroy(stark_ctx* ctx) {
     t = nullptr;
   }
   for (stark_merkle_tree* t : ctx->fri_trees) stark_merkle_free(t);
+  for (stark_merkle_forest* f : ctx->fri_forests) stark_merkle_forest_free(f);
+  ctx->fri_forests.clear();
   for (void* p : ctx->pinned)
     if (p) hipHostFree(p);
   for (auto& kv : ctx->ext_idx)
@@ -331,7 +333,7 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   if (ctx->aux) hipStreamDestroy(ctx->aux);
   ctx->fri_trees.clear();
   for (DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena, &ctx->trace_raw, &ctx->fri_misc,
-                     &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly}) {
+                     &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly}) {
     if (b->ptr) hipFree(b->ptr);
     if (b->ev) hipEventDestroy(b->ev);
   }
@@ -362,11 +364,14 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   size_t total = cached;
   for (const auto& kv : ctx->tw) total += kv.second->base_bytes;
   for (const DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena,
-                          &ctx->trace_raw, &ctx->fri_misc, &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde,
-                          &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly})
+                          &ctx->trace_raw, &ctx->fri_misc, &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena,
+                          &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly})
     total += b->ptr ? b->bytes : 0;
   for (const stark_merkle_tree* t : ctx->trees) total += merkle_device_bytes(t);
   for (const stark_merkle_tree* t : ctx->fri_trees) total += merkle_device_bytes(t);
+  // prove_low_degree_batch's forests and its staging (pinned slot 5 is host memory the device writes)
+  for (const stark_merkle_forest* f : ctx->fri_forests) total += forest_device_bytes(f);
+  total += ctx->pinned_bytes[5];
   if (cached_bytes) *cached_bytes = cached;
   if (cache_limit) *cache_limit = ctx->cache_limit;
   if (resident_bytes) *resident_bytes = total;

@@ -114,12 +114,14 @@ struct FriIdxArgs {
 };
 // One 64-lane workgroup per layer: a quad of lanes hashes the chain (hash_pair_quad, merkle_dev.h; one
 // compression's latency is about a quarter of a lane's), then 40 lanes write one index each.
-__global__ __launch_bounds__(64) void fri_indices_kernel(FriIdxArgs a, uint32_t excl, uint64_t* __restrict__ idx) {
-  __shared__ uint32_t data[40];   // 160 bytes, little-endian words
-  __shared__ uint32_t msg[16];
-  const uint32_t l = blockIdx.x, t = threadIdx.x;
+// The workgroup's work: the 40 column indices of the layer whose column tree has `root`, at col, and the
+// 160 poly indices at poly; data (40 words) and msg (16 words) are the workgroup's LDS.
+__device__ __forceinline__ void fri_indices_block(const uint32_t* __restrict__ root, uint32_t q, uint32_t excl,
+                                                  uint64_t* __restrict__ col, uint64_t* __restrict__ poly,
+                                                  uint32_t* data, uint32_t* msg) {
+  const uint32_t t = threadIdx.x;
   if (t < 8) {
-    data[t] = a.root[l][t];
+    data[t] = root[t];
     msg[t] = data[t];
   } else if (t < 16) {
     msg[t] = 0;
@@ -139,14 +141,75 @@ __global__ __launch_bounds__(64) void fri_indices_kernel(FriIdxArgs a, uint32_t 
     __syncthreads();
   }
   if (t >= 40) return;
-  const uint32_t q = a.q[l];
   const uint32_t real_mod = excl ? (uint32_t)((uint64_t)q * (excl - 1) / excl) : q;
   const uint32_t w = __builtin_bswap32(data[t]);
   const uint32_t v = w % real_mod;
   const uint64_t y = excl ? v + 1 + v / (excl - 1) : v;
-  idx[a.col_at[l] + t] = y;
+  col[t] = y;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) idx[a.poly_at[l] + 4 * t + j] = y + (uint64_t)q * j;
+  for (int j = 0; j < 4; ++j) poly[4 * t + j] = y + (uint64_t)q * j;
+}
+
+__global__ __launch_bounds__(64) void fri_indices_kernel(FriIdxArgs a, uint32_t excl, uint64_t* __restrict__ idx) {
+  __shared__ uint32_t data[40];   // 160 bytes, little-endian words
+  __shared__ uint32_t msg[16];
+  const uint32_t l = blockIdx.x;
+  fri_indices_block(a.root[l], a.q[l], excl, idx + a.col_at[l], idx + a.poly_at[l], data, msg);
+}
+
+// ---- prove_low_degree for a batch of vectors: every kernel with a proof coordinate ----
+
+// The forests of a batch: forest l holds the batch trees that commit layer l's values.  Tree b's nodes
+// start at nodes[l] + b * stride[l] words, its root at root_at[l] words from there.
+struct FriBatchTrees {
+  const uint32_t* nodes[16];
+  uint64_t stride[16], root_at[16];
+  uint32_t q[16];  // layer l's column length
+};
+
+// fri_fold_kernel for proof blockIdx.y: its layer's values at v + b * 4q, its column to col + b * q, its own
+// special_x s[b], and each output's Blake2s into level 0 of tree b of the next forest (leaf + b * leaf_stride
+// words).
+__global__ void fri_fold_batch_kernel(const fe* __restrict__ v, fe* __restrict__ col, uint64_t q, uint32_t shift,
+                                      const fe* __restrict__ lo, const fe* __restrict__ hi, uint32_t kb,
+                                      const fe* __restrict__ s, fe zeta_m, fe inv4_m, uint32_t* __restrict__ leaf,
+                                      uint64_t leaf_stride) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (i >= q) return;
+  const fe x = fri_fold_row(v + b * 4 * q, col + b * q, i, q, shift, 0, 0, lo, hi, kb, s[b], zeta_m, inv4_m);
+  uint32_t h[8], m[16];
+  b2s_init(h);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) {
+    m[w] = x.w[w];
+    m[8 + w] = 0;
+  }
+  b2s_compress(h, m, 32, 0, true);
+  uint4* d = reinterpret_cast<uint4*>(leaf + b * leaf_stride + 8 * i);
+  d[0] = make_uint4(h[0], h[1], h[2], h[3]);
+  d[1] = make_uint4(h[4], h[5], h[6], h[7]);
+}
+
+// Every root of the batch into one buffer: word w of the root of tree b of forest l at
+// out[(b * n_forests + l) * 8 + w] (thread t is that index).
+__global__ void collect_roots_batch_kernel(FriBatchTrees a, uint32_t n_forests, uint32_t batch,
+                                           uint32_t* __restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 8 * n_forests * batch) return;
+  const uint32_t w = t & 7, l = (t >> 3) % n_forests, b = (t >> 3) / n_forests;
+  out[t] = a.nodes[l][b * a.stride[l] + a.root_at[l] + w];
+}
+
+// fri_indices_kernel on a grid of (layer, proof): request pair (b, l) of the gather owns the 200 index slots
+// from 200 (b layers + l): 40 column indices, then 160 poly indices.
+__global__ __launch_bounds__(64) void fri_indices_batch_kernel(FriBatchTrees a, uint32_t excl,
+                                                               uint64_t* __restrict__ idx) {
+  __shared__ uint32_t data[40];
+  __shared__ uint32_t msg[16];
+  const uint32_t l = blockIdx.x, b = blockIdx.y;
+  const uint32_t* root = a.nodes[l + 1] + b * a.stride[l + 1] + a.root_at[l + 1];  // root2: the column tree's
+  uint64_t* at = idx + 200 * ((uint64_t)b * gridDim.x + l);
+  fri_indices_block(root, a.q[l], excl, at, at + 40, data, msg);
 }
 
 // Pinned slot 1 layout: [0, 2048) mk_r1cs_proof's transcript, [2048, 2560) FRI roots.
@@ -389,6 +452,150 @@ stark_status fri_prove_device(stark_ctx* ctx, const fe* d_values, size_t n, cons
   if (st != STARK_OK) return st;
   std::vector<GatherReq> none;
   return fri_finish(ctx, p.get(), none, out);
+}
+
+// prove_low_degree for `batch` vectors (vector b at d_values + b n) as one chain on the context stream:
+// fri_enqueue and fri_finish with a proof coordinate.  Forest l commits layer l's values of every proof; layer
+// l's columns are batch * q_l elements of ctx->fri_cols, proof b's at b * q_l; special_x of (layer l, proof b)
+// is slot l * batch + b of ctx->fri_batch, written by forest l's root launch.  The openings of all
+// 2 * layers * batch requests come from one gather batch behind the device-derived indices; the roots and the
+// Last values come down behind it into pinned slot 5: one synchronisation for the whole batch.
+stark_status fri_prove_batch_device(stark_ctx* ctx, const fe* d_values, size_t n, uint32_t batch,
+                                    const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,
+                                    stark_fri_proof** out) {
+  const FieldHost& F = FieldHost::get();
+  hipStream_t s = ctx->stream;
+  size_t layers = 0;
+  const Twiddles* tw = nullptr;
+  STARK_TRY(fri_check(ctx, n, root, max_deg_plus_1, excl, &layers, &tw));
+  std::vector<size_t> qs;
+  size_t col_total = 0;
+  for (size_t l = 0, m = n; l < layers; ++l) {
+    m /= 4;
+    qs.push_back(m);
+    col_total += m;
+  }
+  const size_t last_len = n >> (2 * layers);
+  STARK_TRY(ensure_buf(ctx, ctx->fri_cols, (col_total ? col_total * batch : 1) * sizeof(fe)));
+  STARK_TRY(ensure_buf(ctx, ctx->fri_batch, (layers ? layers : 1) * batch * sizeof(fe)));
+  const size_t roots_bytes = (layers + 1) * (size_t)batch * 32, last_bytes = last_len * (size_t)batch * 32;
+  uint8_t* pinned = nullptr;
+  STARK_TRY(ctx_pinned(ctx, 5, roots_bytes + last_bytes, (void**)&pinned));
+  const uint8_t* h_roots = pinned;
+  uint8_t* h_last = pinned + roots_bytes;
+  while (ctx->fri_forests.size() < layers + 1) {
+    stark_merkle_forest* f = nullptr;
+    STARK_TRY(stark_merkle_forest_new(ctx, &f));
+    ctx->fri_forests.push_back(f);
+  }
+  std::vector<stark_merkle_forest*>& forests = ctx->fri_forests;
+
+  fe* d_sx = (fe*)ctx->fri_batch.ptr;
+  const fe* cur = d_values;
+  fe* next = (fe*)ctx->fri_cols.ptr;
+  size_t m = n;
+  HostFp w = F.from_canonical(root);
+  const HostFp inv4 = F.inv(F.from_u64(4));
+  const fe r2 = to_dev(F.from_canonical(F.one().v));  // Montgomery image of R
+  for (size_t layer = 0; layer < layers; ++layer) {
+    bool sx_made = true;
+    // (every folded layer has m >= 8 values, fri_check: its trees' roots come from the forest's tail launch)
+    if (layer == 0)
+      STARK_TRY(forest_build(ctx, forests[0], (const uint8_t*)cur, m, 32, batch, s, false, d_sx, &r2, &sx_made));
+    const size_t q = m / 4;
+    const HostFp zeta = F.pow_u64(w, q);  // w^(n/4)
+    uint32_t* leaf = nullptr;
+    size_t leaf_stride = 0;
+    STARK_TRY(forest_level0(ctx, forests[layer + 1], q, batch, &leaf, &leaf_stride));
+    hipLaunchKernelGGL(fri_fold_batch_kernel, dim3((unsigned)((q + 255) / 256), batch), dim3(256), 0, s, cur, next,
+                       (uint64_t)q, (uint32_t)(2 * layer), tw->d_lo, tw->d_hi, tw->kb,
+                       (const fe*)(d_sx + layer * batch), to_dev(zeta), to_dev(inv4), leaf, (uint64_t)leaf_stride);
+    STARK_HIP(ctx, hipGetLastError());
+    const bool more = layer + 1 < layers;
+    bool next_made = true;
+    STARK_TRY(forest_build(ctx, forests[layer + 1], (const uint8_t*)next, q, 32, batch, s, true,
+                           more ? d_sx + (layer + 1) * batch : nullptr, &r2, more ? &next_made : nullptr));
+    if (!sx_made || !next_made) {
+      ctx->last_error = "prove_low_degree_batch: a forest did not make its roots' field elements";
+      return STARK_ERR_STATE;
+    }
+    cur = next;
+    next += (size_t)batch * q;
+    m = q;
+    w = F.pow_u64(w, 4);  // fri.rs:215-223
+  }
+  // Roots and the Last layer's values (fri.rs:108-110; contiguous over the batch), then indices and gather.
+  FriBatchTrees bt{};
+  for (size_t l = 0; l <= layers && layers; ++l) {
+    bt.nodes[l] = forest_nodes_dev(forests[l], &bt.stride[l], &bt.root_at[l]);
+    if (l < layers) bt.q[l] = (uint32_t)qs[l];
+  }
+  if (layers) {
+    const uint32_t words = 8 * (uint32_t)(layers + 1) * batch;
+    hipLaunchKernelGGL(collect_roots_batch_kernel, dim3((words + 255) / 256), dim3(256), 0, s, bt,
+                       (uint32_t)(layers + 1), batch, (uint32_t*)pinned);
+    STARK_HIP(ctx, hipGetLastError());
+  }
+  if (last_bytes) STARK_HIP(ctx, hipMemcpyAsync(h_last, cur, last_bytes, hipMemcpyDeviceToHost, s));
+
+  std::vector<std::unique_ptr<stark_fri_proof>> proofs(batch);
+  std::vector<GatherReq> reqs;
+  reqs.reserve(2 * layers * batch);
+  for (uint32_t b = 0; b < batch; ++b) {
+    proofs[b] = std::make_unique<stark_fri_proof>();
+    proofs[b]->layers.resize(layers);
+    for (size_t layer = 0; layer < layers; ++layer) {
+      stark_fri_layer& L = proofs[b]->layers[layer];
+      L.col_idx.resize(40);
+      L.poly_idx.resize(160);
+      L.col_depth = 0;
+      while (((size_t)1 << L.col_depth) < qs[layer]) ++L.col_depth;
+      L.poly_depth = L.col_depth + 2;
+      L.col_leaves.resize(40 * 32);
+      L.col_nodes.resize(40 * L.col_depth * 32);
+      L.poly_leaves.resize(160 * 32);
+      L.poly_nodes.resize(160 * L.poly_depth * 32);
+      reqs.push_back({forest_tree(forests[layer + 1], b), nullptr, 40, L.col_leaves.data(), L.col_nodes.data()});
+      reqs.push_back({forest_tree(forests[layer], b), nullptr, 160, L.poly_leaves.data(), L.poly_nodes.data()});
+    }
+  }
+  const uint64_t* h_idx = nullptr;
+  auto indices = [&](uint64_t* hi, const std::vector<size_t>& first) -> stark_status {
+    h_idx = hi;
+    for (size_t r = 0; r < first.size(); r += 2)  // (the slots fri_indices_batch_kernel writes)
+      if (first[r] != 100 * r || first[r + 1] != 100 * r + 40) return STARK_ERR_STATE;
+    hipLaunchKernelGGL(fri_indices_batch_kernel, dim3((unsigned)layers, batch), dim3(64), 0, s, bt, excl, hi);
+    STARK_HIP(ctx, hipGetLastError());
+    return STARK_OK;
+  };
+  if (layers) STARK_TRY(merkle_gather_batch(ctx, reqs, s, indices));
+  else STARK_HIP(ctx, hipStreamSynchronize(s));  // (no gather: the Last values' copy)
+
+  for (uint32_t b = 0; b < batch; ++b) {
+    stark_fri_proof* proof = proofs[b].get();
+    for (size_t layer = 0; layer < layers; ++layer) {
+      stark_fri_layer& L = proof->layers[layer];
+      memcpy(L.root2, h_roots + 32 * (b * (layers + 1) + layer + 1), 32);
+      // ys = get_pseudorandom_indices(m2_root, column.len(), 40, exclude) (fri.rs:181-189), checked per proof
+      uint32_t ys[40];
+      STARK_TRY(stark_get_pseudorandom_indices(L.root2, 32, (uint32_t)qs[layer], 40, excl, ys));
+      const uint64_t* at = h_idx + 200 * (b * layers + layer);
+      for (int i = 0; i < 40; ++i) {
+        L.col_idx[i] = (size_t)at[i];
+        for (int j = 0; j < 4; ++j) L.poly_idx[4 * i + j] = (size_t)at[40 + 4 * i + j];
+        if (L.col_idx[i] != ys[i]) {
+          ctx->last_error = "FRI indices derived on the device differ from the host's";
+          return STARK_ERR_HIP;
+        }
+      }
+    }
+    stark_fri_layer last;
+    last.last = true;
+    last.last_values.assign(h_last + (size_t)b * last_len * 32, h_last + (size_t)(b + 1) * last_len * 32);
+    proof->layers.push_back(std::move(last));
+  }
+  for (uint32_t b = 0; b < batch; ++b) out[b] = proofs[b].release();
+  return STARK_OK;
 }
 
 // "[b0,b1,...]" for a byte string (serde_json of Vec<u8>), table driven: each byte is one 4-byte store
@@ -715,6 +922,34 @@ stark_status stark_prove_low_degree(stark_ctx* ctx, const uint64_t* values, size
   if (st != STARK_OK) return st;
   if (n) STARK_HIP(ctx, hipMemcpyAsync(ctx->io.ptr, values, n * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
   st = fri_prove_device(ctx, (const fe*)ctx->io.ptr, n, root, max_deg_plus_1, exclude_multiples_of, out);
+  hipStreamSynchronize(ctx->stream);
+  return st;
+}
+
+constexpr uint32_t kFriMaxBatch = 65535;  // a forest's (the proof coordinate is grid.y)
+
+stark_status stark_prove_low_degree_batch_dev(stark_ctx* ctx, const uint64_t* d_values, size_t n, uint32_t batch,
+                                              const uint64_t root[4], size_t max_deg_plus_1,
+                                              uint32_t exclude_multiples_of, stark_fri_proof** out) {
+  if (!ctx || !root || (batch && (!out || (n && !d_values))) || batch > kFriMaxBatch) return STARK_ERR_BAD_ARG;
+  if (batch == 0) return STARK_OK;
+  for (uint32_t b = 0; b < batch; ++b) out[b] = nullptr;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  return fri_prove_batch_device(ctx, (const fe*)d_values, n, batch, root, max_deg_plus_1, exclude_multiples_of, out);
+}
+
+stark_status stark_prove_low_degree_batch(stark_ctx* ctx, const uint64_t* values, size_t n, uint32_t batch,
+                                          const uint64_t root[4], size_t max_deg_plus_1,
+                                          uint32_t exclude_multiples_of, stark_fri_proof** out) {
+  if (!ctx || !root || (batch && (!out || (n && !values))) || batch > kFriMaxBatch) return STARK_ERR_BAD_ARG;
+  if (batch == 0) return STARK_OK;
+  for (uint32_t b = 0; b < batch; ++b) out[b] = nullptr;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)batch * n * sizeof(fe);
+  STARK_TRY(ensure_buf(ctx, ctx->io, bytes ? bytes : sizeof(fe)));
+  if (bytes) STARK_HIP(ctx, hipMemcpyAsync(ctx->io.ptr, values, bytes, hipMemcpyHostToDevice, ctx->stream));
+  const stark_status st = fri_prove_batch_device(ctx, (const fe*)ctx->io.ptr, n, batch, root, max_deg_plus_1,
+                                                 exclude_multiples_of, out);
   hipStreamSynchronize(ctx->stream);
   return st;
 }

@@ -172,8 +172,12 @@ struct stark_ctx {
   stark_merkle_tree* trees[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   std::vector<stark_merkle_tree*> fri_trees;  // one per FRI layer (+ the input's), reused across proofs
   stark::DevBuf fri_misc;                     // per-layer special_x (device transcript)
-  void* pinned[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // pinned host scratch (ctx_pinned)
-  size_t pinned_bytes[5] = {0, 0, 0, 0, 0};
+  // prove_low_degree_batch: one forest per FRI layer (+ the inputs'), special_x per (layer, proof); reused and
+  // grown across calls, as pinned slot 5 (the batch's roots and Last values).
+  std::vector<stark_merkle_forest*> fri_forests;
+  stark::DevBuf fri_batch;
+  void* pinned[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // pinned host scratch (ctx_pinned)
+  size_t pinned_bytes[6] = {0, 0, 0, 0, 0, 0};
   hipEvent_t staged = nullptr;  // the last DMA out of pinned slot 3 (r1cs_trace_dev.hip staged_upload)
   // A second stream and an event for work the host overlaps with the main stream (the prover's spot-check
   // openings gathered while its FRI layers still run, r1cs.hip); created on first use.
@@ -243,7 +247,8 @@ bool cache_reserve(stark_ctx* ctx, size_t need, bool evict_ext);
 // Slot 0: gather batches; slot 1: transcript values and roots; slot 2: the device trace builder's
 // record-walk tables; slot 3: its upload staging (the raw .r1cs constraint section and witness); slot 4:
 // the prover's small host-made uploads (constraint tables at 0, boundary constants from kPinned4ConstsOff),
-// so they are asynchronous copies (a pageable copy blocks the host).
+// so they are asynchronous copies (a pageable copy blocks the host).  Slot 5: prove_low_degree_batch's roots
+// and Last values (it grows with the batch; slot 1's fixed layout stays the single proof's).
 constexpr size_t kPinned4ConstsOff = 16384;
 stark_status ctx_pinned(stark_ctx* ctx, int slot, size_t bytes, void** out);
 // Pinned slot 1 (always this size, so no caller's pointer into it moves): [0, 2048) the prover's
@@ -393,6 +398,21 @@ struct GatherReq {
 using GatherHook = std::function<stark_status(uint64_t* h_idx, const std::vector<size_t>& first)>;
 stark_status merkle_gather_batch(stark_ctx* ctx, const std::vector<GatherReq>& reqs, hipStream_t stream,
                                  const GatherHook& before_launch = GatherHook());
+
+// Merkle forest internals (merkle.hip): `batch` trees of n leaves by one set of launches, tree b's leaves at
+// d_leaves + b n leaf_len.  forest_level0 / forest_build(..., level0_ready) as merkle_level0 / merkle_build:
+// tree b's leaf digests go to *level0 + b * *stride_words.  fe_out non-null: the launch that makes the roots
+// writes root b as a field element (RootFe's role, with *r2) to fe_out[b]; *fe_made tells whether one did.
+stark_status forest_level0(stark_ctx* ctx, stark_merkle_forest* f, size_t n, uint32_t batch, uint32_t** level0,
+                           size_t* stride_words);
+stark_status forest_build(stark_ctx* ctx, stark_merkle_forest* f, const uint8_t* d_leaves, size_t n, size_t leaf_len,
+                          uint32_t batch, hipStream_t stream, bool level0_ready = false, fe* fe_out = nullptr,
+                          const fe* r2 = nullptr, bool* fe_made = nullptr);
+// Tree b as the gather code and merkle_root_dev read a tree (owned by the forest, valid until its next build).
+stark_merkle_tree* forest_tree(stark_merkle_forest* f, uint32_t b);
+// Tree 0's nodes as words, with the words from a tree to the next and from a tree's first node to its root.
+const uint32_t* forest_nodes_dev(const stark_merkle_forest* f, uint64_t* stride_words, uint64_t* root_word);
+size_t forest_device_bytes(const stark_merkle_forest* f);  // device memory the forest owns (0 for null)
 
 // A rendered JSON text: one uninitialised allocation written once (a std::string would be
 // zero-filled first), so a multi-MB proof is assembled by several threads in parallel.
@@ -623,6 +643,11 @@ stark_status fri_enqueue(stark_ctx* ctx, const fe* d_values, size_t n, const uin
 stark_status fri_finish(stark_ctx* ctx, FriPending* p, std::vector<GatherReq>& extra, stark_fri_proof** out);
 stark_status fri_prove_device(stark_ctx* ctx, const fe* d_values, size_t n, const uint64_t root[4],
                               size_t max_deg_plus_1, uint32_t excl, stark_fri_proof** out);
+// prove_low_degree for `batch` vectors of n device values (vector b at d_values + b n) through one launch chain
+// and one synchronisation (fri.hip): out[b] = fri_prove_device's proof of vector b; on an error no out[b] is set.
+stark_status fri_prove_batch_device(stark_ctx* ctx, const fe* d_values, size_t n, uint32_t batch,
+                                    const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,
+                                    stark_fri_proof** out);
 // prove_low_degree's argument checks alone (fri.hip): the status fri_enqueue returns for these arguments
 // before it enqueues anything.  n_layers / tw_out may be null.
 stark_status fri_check(stark_ctx* ctx, size_t n, const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,

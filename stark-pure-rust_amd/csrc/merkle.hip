@@ -34,6 +34,21 @@ struct stark_merkle_tree {
   stark::DevBuf gather;              // scratch for proof gathers
 };
 
+// `batch` trees of n leaves each, built by one set of launches (forest_build below).  Tree-major: tree b's
+// 2n - 1 digests are contiguous (level-major, as a single tree's) at nodes + b * stride digests, and its
+// leaves at d_leaves + b * n * leaf_len.  views[b] presents tree b to the gather code (and to
+// merkle_root_dev) as a stark_merkle_tree that owns nothing.
+struct stark_merkle_forest {
+  stark_ctx* ctx = nullptr;
+  size_t n = 0, leaf_len = 0, stride = 0;  // stride = 2n - 1 digests
+  uint32_t depth = 0, batch = 0;
+  stark::DevBuf nodes;                     // batch * stride * 32 B
+  stark::DevBuf own_leaves;                // leaves copied from the host
+  const uint8_t* d_leaves = nullptr;
+  bool built = false;
+  std::vector<stark_merkle_tree> views;
+};
+
 namespace stark {
 
 constexpr uint32_t kMerkleBlock = 1024;   // nodes per workgroup at its input level
@@ -629,6 +644,247 @@ stark_status merkle_gather_batch(stark_ctx* ctx, const std::vector<GatherReq>& r
   return STARK_OK;
 }
 
+// ---- Merkle forest: `batch` equal-shaped trees by one set of launches ----
+//
+// The launches are the single tree's with a tree coordinate: the wide levels (and the leaf level) hash one
+// node per lane over the whole forest (grid.y = the tree), the narrow levels hash on quads of lanes in LDS.
+// A forest amortises its launches over its trees, so there is no fused "last workgroup" top: a tree with
+// more than kTailBlock nodes at a narrow level takes one more launch, and no forest kernel uses an atomic or
+// orders workgroups.  Once a tree's level has at most kTailBlock nodes, kTailBlock / count trees share a
+// workgroup and go to their roots in that launch, which also writes each root as a field element (RootFe's
+// role; tree b's to fe_out + b).
+
+// Where a launch's levels are: digest offsets inside a tree's 2n - 1 nodes, the same for every tree.
+struct ForestLevels {
+  Digest* nodes;    // tree 0's level 0
+  uint64_t stride;  // digests from a tree to the next
+  uint64_t below;   // the level the pairs are read from (pair mode)
+  uint64_t lv[9];   // the input level and the levels above it
+};
+
+// merkle_build_kernel's work for tree blockIdx.y: `block` nodes of the input level per workgroup (leaf mode:
+// from tree's leaves; pair mode: from the level below), then `extra` <= 2 more levels in LDS.
+template <bool LEAF32>
+__global__ __launch_bounds__(kMerkleThreads) void forest_build_kernel(const uint8_t* __restrict__ leaves,
+                                                                      uint32_t leaf_len, uint64_t n, ForestLevels f,
+                                                                      uint64_t count, uint32_t block,
+                                                                      uint32_t extra) {
+  __shared__ __attribute__((aligned(16))) Digest lds[kMerkleBlock];
+  const uint64_t tree = blockIdx.y;
+  Digest* nodes = f.nodes + tree * f.stride;
+  const uint64_t base = (uint64_t)blockIdx.x * block;
+  const uint32_t here = (uint32_t)((count - base) < block ? (count - base) : block);
+  if (leaves) {  // (uniform)
+    const uint8_t* mine = leaves + tree * n * leaf_len;
+    for (uint32_t i = threadIdx.x; i < here; i += blockDim.x) {
+      const uint64_t node = base + i;
+      const Digest d = LEAF32 ? hash_leaf32(mine + node * 32) : hash_leaf(mine + node * leaf_len, leaf_len);
+      store_digest(nodes + f.lv[0] + node, d);
+      lds[i] = d;
+    }
+  } else {
+    const Digest* below = nodes + f.below + 2 * base;
+    for (uint32_t i = threadIdx.x; i < here; i += blockDim.x) {
+      const Digest d = hash_pair(load_digest(below + 2 * i), load_digest(below + 2 * i + 1));
+      store_digest(nodes + f.lv[0] + base + i, d);
+      lds[i] = d;
+    }
+  }
+  __syncthreads();
+  uint32_t width = here;
+  for (uint32_t k = 1; k <= extra; ++k) {
+    width >>= 1;  // <= kMerkleBlock / 2: two pair hashes per thread per level
+    const uint32_t i0 = threadIdx.x, i1 = threadIdx.x + blockDim.x;
+    Digest r0, r1;
+    if (i0 < width) r0 = hash_pair(lds[2 * i0], lds[2 * i0 + 1]);
+    if (i1 < width) r1 = hash_pair(lds[2 * i1], lds[2 * i1 + 1]);
+    __syncthreads();
+    if (i0 < width) {
+      lds[i0] = r0;
+      store_digest(nodes + f.lv[k] + (base >> k) + i0, r0);
+    }
+    if (i1 < width) {
+      lds[i1] = r1;
+      store_digest(nodes + f.lv[k] + (base >> k) + i1, r1);
+    }
+    __syncthreads();
+  }
+}
+
+// Narrow pair levels.  tpw == 1: grid (blocks of kTailBlock nodes, trees), each block reduced `extra` more
+// levels by tail_levels as in merkle_tail_kernel.  tpw > 1 (count = 2^extra <= kTailBlock / 2 nodes per
+// tree): workgroup g holds trees [g tpw, (g + 1) tpw) side by side in LDS, tree t's nodes at slots
+// [t count, (t + 1) count); a level's pairs never straddle two trees, so the slots reduce as one block and only
+// the stores tell the trees apart: every tree ends at its root.
+// fe_out non-null (only where the launch makes the roots): tree b's root as a field element into fe_out[b].
+__global__ __launch_bounds__(kTailThreads) void forest_tail_kernel(ForestLevels f, uint32_t count, uint32_t extra,
+                                                                   uint32_t batch, uint32_t tpw,
+                                                                   fe* __restrict__ fe_out, fe r2) {
+  __shared__ __attribute__((aligned(16))) uint32_t msg[2 * kTailBlock * 8];
+  if (tpw == 1) {  // (uniform)
+    const uint64_t tree = blockIdx.y;
+    Digest* nodes = f.nodes + tree * f.stride;
+    const uint64_t base = (uint64_t)blockIdx.x * kTailBlock;
+    const uint32_t here = (uint32_t)((count - base) < kTailBlock ? (count - base) : kTailBlock);
+    const uint4* src = reinterpret_cast<const uint4*>(nodes + f.below + 2 * base);
+    for (uint32_t i = threadIdx.x; i < here * 4; i += blockDim.x) reinterpret_cast<uint4*>(msg)[i] = src[i];
+    __syncthreads();
+    LevelPtrs out;
+    for (uint32_t k = 0; k <= extra; ++k) out.lv[k] = nodes + f.lv[k];
+    tail_levels(msg, base, here, extra, out, false);
+    if (fe_out && threadIdx.x == 0) root_fe_out(msg, RootFe{fe_out + tree, r2, nullptr, true});
+    return;
+  }
+  const uint32_t tree0 = blockIdx.x * tpw;
+  const uint32_t nt = batch - tree0 < tpw ? batch - tree0 : tpw;
+  const uint32_t total = nt << extra;  // slots of the input level (<= kTailBlock)
+  for (uint32_t i = threadIdx.x; i < total * 4; i += blockDim.x) {
+    const uint32_t slot = i >> 2, t = slot >> extra, nd = slot & (count - 1);
+    const uint4* src = reinterpret_cast<const uint4*>(f.nodes + (uint64_t)(tree0 + t) * f.stride + f.below + 2 * nd);
+    reinterpret_cast<uint4*>(msg)[i] = src[i & 3];
+  }
+  __syncthreads();
+  const uint32_t slot = threadIdx.x >> 2, q = threadIdx.x & 3;
+  uint32_t width = total;
+  for (uint32_t k = 0; k <= extra; ++k) {
+    const bool active = slot < width;
+    uint32_t lo = 0, hi = 0;
+    if (active) hash_pair_quad(msg + slot * 16, q, lo, hi);
+    __syncthreads();
+    if (active) {
+      msg[slot * 8 + q] = lo;
+      msg[slot * 8 + 4 + q] = hi;
+      const uint32_t t = slot >> (extra - k), nd = slot & ((count >> k) - 1);
+      uint32_t* g = reinterpret_cast<uint32_t*>(f.nodes + (uint64_t)(tree0 + t) * f.stride + f.lv[k] + nd);
+      g[q] = lo;
+      g[4 + q] = hi;
+    }
+    __syncthreads();
+    width >>= 1;
+  }
+  // (slot t now holds tree tree0 + t's root)
+  if (fe_out && threadIdx.x < nt)
+    root_fe_out(msg + 8 * threadIdx.x, RootFe{fe_out + tree0 + threadIdx.x, r2, nullptr, true});
+}
+
+constexpr uint32_t kForestMaxBatch = 65535;  // the tree coordinate is grid.y
+
+static stark_status forest_check(size_t n, size_t leaf_len, uint32_t batch) {
+  if (n == 0 || (n & (n - 1)) != 0) return STARK_ERR_BAD_LENGTH;
+  if (batch == 0 || batch > kForestMaxBatch || leaf_len > 0xFFFFFFFFull) return STARK_ERR_BAD_ARG;
+  return STARK_OK;
+}
+
+static stark_status forest_nodes(stark_ctx* ctx, stark_merkle_forest* f, size_t n, uint32_t batch) {
+  return ensure_buf(ctx, f->nodes, (size_t)batch * (2 * n - 1) * sizeof(Digest));
+}
+
+// Level 0 of every tree (the leaf digests, 8 words each; tree b's at *level0 + b * *stride_words), for a
+// kernel that hashes the leaves as it makes them; forest_build(..., level0_ready) then builds the levels above.
+stark_status forest_level0(stark_ctx* ctx, stark_merkle_forest* f, size_t n, uint32_t batch, uint32_t** level0,
+                           size_t* stride_words) {
+  STARK_TRY(forest_check(n, 32, batch));
+  STARK_TRY(forest_nodes(ctx, f, n, batch));
+  *level0 = reinterpret_cast<uint32_t*>(f->nodes.ptr);
+  *stride_words = (2 * n - 1) * 8;
+  return STARK_OK;
+}
+
+// Builds every level of the batch trees over d_leaves (tree b: n leaves of leaf_len bytes at
+// d_leaves + b n leaf_len); with level0_ready level 0 is already in place (the proofs still open d_leaves).
+// fe_out non-null: the launch that makes the roots also writes root b as a field element to fe_out[b]
+// (*fe_made tells whether one did: every tree of depth >= 1).
+stark_status forest_build(stark_ctx* ctx, stark_merkle_forest* f, const uint8_t* d_leaves, size_t n, size_t leaf_len,
+                          uint32_t batch, hipStream_t stream, bool level0_ready, fe* fe_out, const fe* r2,
+                          bool* fe_made) {
+  if (fe_made) *fe_made = false;
+  STARK_TRY(forest_check(n, leaf_len, batch));
+  uint32_t depth = 0;
+  while (((size_t)1 << depth) < n) ++depth;
+  STARK_TRY(forest_nodes(ctx, f, n, batch));
+  ForestLevels fl{};
+  fl.nodes = (Digest*)f->nodes.ptr;
+  fl.stride = 2 * n - 1;
+  uint32_t level = level0_ready ? 1 : 0;
+  uint64_t count = level0_ready ? n / 2 : n;
+  bool leaf_mode = !level0_ready;
+  while (depth > 0 || !level0_ready) {
+    fl.below = level ? level_offset(n, level - 1) : 0;
+    if (!leaf_mode && count < kTailFrom) {
+      const uint64_t blk = count < kTailBlock ? count : kTailBlock;
+      uint32_t extra = 0;
+      while ((blk >> (extra + 1)) >= 1 && level + extra + 1 <= depth) ++extra;
+      for (uint32_t k = 0; k <= extra; ++k) fl.lv[k] = level_offset(n, level + k);
+      const bool to_root = count <= kTailBlock;  // (then extra = log2(count): level + extra = depth)
+      const uint32_t tpw = to_root ? (uint32_t)(kTailBlock / count) : 1;
+      const dim3 grid = tpw > 1 ? dim3((batch + tpw - 1) / tpw)
+                                : dim3((unsigned)((count + kTailBlock - 1) / kTailBlock), batch);
+      const bool fe_here = to_root && fe_out;
+      hipLaunchKernelGGL(forest_tail_kernel, grid, dim3(kTailThreads), 0, stream, fl, (uint32_t)count, extra, batch,
+                         tpw, fe_here ? fe_out : (fe*)nullptr, fe_here ? *r2 : fe{});
+      STARK_HIP(ctx, hipGetLastError());
+      if (fe_here && fe_made) *fe_made = true;
+      level += extra;
+      count >>= extra;
+    } else {
+      const bool narrow_leaf = count < kTailFrom;
+      const uint32_t block = narrow_leaf ? kMerkleThreads : kMerkleBlock;
+      const uint64_t blk = count < block ? count : block;
+      const uint32_t max_extra = narrow_leaf ? 0 : 2;
+      uint32_t extra = 0;
+      while ((blk >> (extra + 1)) >= 1 && extra + 1 <= max_extra && level + extra + 1 <= depth) ++extra;
+      for (uint32_t k = 0; k <= extra; ++k) fl.lv[k] = level_offset(n, level + k);
+      const dim3 grid((unsigned)((count + block - 1) / block), batch);
+      const bool leaf32 = leaf_mode && leaf_len == 32 && (((uintptr_t)d_leaves) & 15) == 0;
+      hipLaunchKernelGGL(leaf32 ? forest_build_kernel<true> : forest_build_kernel<false>, grid, dim3(kMerkleThreads),
+                         0, stream, leaf_mode ? d_leaves : (const uint8_t*)nullptr, (uint32_t)leaf_len, (uint64_t)n,
+                         fl, count, block, extra);
+      STARK_HIP(ctx, hipGetLastError());
+      level += extra;
+      count >>= extra;
+    }
+    if (level == depth) break;
+    ++level;
+    count >>= 1;
+    leaf_mode = false;
+  }
+  f->n = n;
+  f->leaf_len = leaf_len;
+  f->stride = 2 * n - 1;
+  f->depth = depth;
+  f->batch = batch;
+  f->d_leaves = d_leaves;
+  f->built = true;
+  f->views.resize(batch);
+  for (uint32_t b = 0; b < batch; ++b) {
+    stark_merkle_tree& v = f->views[b];
+    v.ctx = ctx;
+    v.n = n;
+    v.leaf_len = leaf_len;
+    v.depth = depth;
+    v.nodes.ptr = (Digest*)f->nodes.ptr + (size_t)b * f->stride;
+    v.nodes.bytes = f->stride * sizeof(Digest);
+    v.d_leaves = d_leaves + (size_t)b * n * leaf_len;
+    v.plane_stride = 0;
+    v.built = true;
+  }
+  return STARK_OK;
+}
+
+stark_merkle_tree* forest_tree(stark_merkle_forest* f, uint32_t b) { return &f->views[b]; }
+
+// Tree 0's nodes as words, with the words from a tree to the next and from a tree's level 0 to its root.
+const uint32_t* forest_nodes_dev(const stark_merkle_forest* f, uint64_t* stride_words, uint64_t* root_word) {
+  *stride_words = (uint64_t)f->stride * 8;
+  *root_word = (uint64_t)(2 * f->n - 2) * 8;
+  return (const uint32_t*)f->nodes.ptr;
+}
+
+size_t forest_device_bytes(const stark_merkle_forest* f) {
+  if (!f) return 0;
+  return (f->nodes.ptr ? f->nodes.bytes : 0) + (f->own_leaves.ptr ? f->own_leaves.bytes : 0);
+}
+
 }  // namespace stark
 
 using namespace stark;
@@ -779,6 +1035,70 @@ stark_status stark_merkle_gen_proofs(stark_merkle_tree* t, const size_t* indices
   if (st != STARK_OK) return st;
   t->has_root = true;
   return merkle_gather(ctx, t, indices, k, leaves_out, nodes_out, ctx->stream, true);
+}
+
+stark_status stark_merkle_forest_new(stark_ctx* ctx, stark_merkle_forest** out) {
+  if (!ctx || !out) return STARK_ERR_BAD_ARG;
+  stark_merkle_forest* f = new (std::nothrow) stark_merkle_forest();
+  if (!f) return STARK_ERR_OOM;
+  f->ctx = ctx;
+  *out = f;
+  return STARK_OK;
+}
+
+void stark_merkle_forest_free(stark_merkle_forest* f) {
+  if (!f) return;
+  hipSetDevice(f->ctx->device);
+  if (f->nodes.ptr) hipFree(f->nodes.ptr);
+  if (f->own_leaves.ptr) hipFree(f->own_leaves.ptr);
+  delete f;  // (the views own nothing)
+}
+
+stark_status stark_merkle_forest_update(stark_merkle_forest* f, const uint8_t* leaves, size_t n, size_t leaf_len,
+                                        uint32_t batch) {
+  if (!f) return STARK_ERR_BAD_ARG;
+  STARK_TRY(forest_check(n, leaf_len, batch));
+  const size_t bytes = (size_t)batch * n * leaf_len;
+  if (!leaves && bytes) return STARK_ERR_BAD_ARG;
+  stark_ctx* ctx = f->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  STARK_TRY(ensure_buf(ctx, f->own_leaves, bytes ? bytes : 16));
+  if (bytes) STARK_HIP(ctx, hipMemcpyAsync(f->own_leaves.ptr, leaves, bytes, hipMemcpyHostToDevice, ctx->stream));
+  STARK_TRY(forest_build(ctx, f, (const uint8_t*)f->own_leaves.ptr, n, leaf_len, batch, ctx->stream));
+  STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return STARK_OK;
+}
+
+stark_status stark_merkle_forest_update_dev(stark_merkle_forest* f, const uint8_t* d_leaves, size_t n,
+                                            size_t leaf_len, uint32_t batch, void* stream) {
+  if (!f) return STARK_ERR_BAD_ARG;
+  STARK_TRY(forest_check(n, leaf_len, batch));
+  if (!d_leaves) return STARK_ERR_BAD_ARG;
+  stark_ctx* ctx = f->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  return forest_build(ctx, f, d_leaves, n, leaf_len, batch, pick_stream(ctx, stream));
+}
+
+stark_status stark_merkle_forest_roots(stark_merkle_forest* f, uint8_t* roots) {
+  if (!f || !roots) return STARK_ERR_BAD_ARG;
+  if (!f->built) return STARK_ERR_STATE;
+  stark_ctx* ctx = f->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  // one strided copy: root b is the last digest of tree b
+  STARK_HIP(ctx, hipMemcpy2DAsync(roots, 32, merkle_root_dev(&f->views[0]), f->stride * sizeof(Digest), 32,
+                                  f->batch, hipMemcpyDeviceToHost, ctx->stream));
+  STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return STARK_OK;
+}
+
+stark_status stark_merkle_forest_gen_proofs(stark_merkle_forest* f, uint32_t tree, const size_t* indices, size_t k,
+                                            uint8_t* leaves_out, uint8_t* nodes_out) {
+  if (!f || (k && !indices)) return STARK_ERR_BAD_ARG;
+  if (!f->built) return STARK_ERR_STATE;
+  if (tree >= f->batch) return STARK_ERR_BAD_ARG;
+  stark_ctx* ctx = f->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  return merkle_gather_batch(ctx, {GatherReq{&f->views[tree], indices, k, leaves_out, nodes_out}}, ctx->stream);
 }
 
 stark_status stark_merkle_verify(const uint8_t root[32], const size_t* indices, size_t k, const uint8_t* leaves,

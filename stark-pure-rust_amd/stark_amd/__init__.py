@@ -89,6 +89,17 @@ _SIGNATURES = {
     "stark_merkle_gen_proofs": ([_vp, _szp, ctypes.c_size_t, _u8p, _u8p], ctypes.c_int),
     "stark_merkle_verify": ([_u8p, _szp, ctypes.c_size_t, _u8p, ctypes.c_size_t, _u8p, ctypes.c_size_t],
                             ctypes.c_int),
+    "stark_merkle_forest_new": ([_vp, ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_merkle_forest_free": ([_vp], None),
+    "stark_merkle_forest_update": ([_vp, _u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32], ctypes.c_int),
+    "stark_merkle_forest_update_dev": ([_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, _vp],
+                                       ctypes.c_int),
+    "stark_merkle_forest_roots": ([_vp, _u8p], ctypes.c_int),
+    "stark_merkle_forest_gen_proofs": ([_vp, ctypes.c_uint32, _szp, ctypes.c_size_t, _u8p, _u8p], ctypes.c_int),
+    "stark_prove_low_degree_batch": ([_vp, _u64p, ctypes.c_size_t, ctypes.c_uint32, _u64p, ctypes.c_size_t,
+                                      ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_prove_low_degree_batch_dev": ([_vp, _vp, ctypes.c_size_t, ctypes.c_uint32, _u64p, ctypes.c_size_t,
+                                          ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_prove_low_degree": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, ctypes.c_uint32,
                                 ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_prove_low_degree_dev": ([_vp, _vp, ctypes.c_size_t, _u64p, ctypes.c_size_t, ctypes.c_uint32,
@@ -592,6 +603,30 @@ class Context:
                                                        exclude_multiples_of, ctypes.byref(h)), "prove_low_degree")
         return FriProofList(self.lib, h)
 
+    def prove_low_degree_batch(self, values, root_of_unity, max_deg_plus_1: int, exclude_multiples_of: int) -> list:
+        """prove_low_degree (fri.rs:46-62) of every vector of `values`, a (batch, n, 4) uint64 array or a list
+        of equally long vectors, through one launch chain: a list of FriProofList, each equal to
+        prove_low_degree's for its vector."""
+        vs = [_elems(v) for v in values]
+        if len({len(v) for v in vs}) > 1:
+            raise ValueError("prove_low_degree_batch: vectors of one length")
+        if not vs:
+            return []
+        v = np.ascontiguousarray(np.stack(vs))
+        return self._prove_batch(self.lib.stark_prove_low_degree_batch, _p64(v), v.shape[1], len(vs), root_of_unity,
+                                 max_deg_plus_1, exclude_multiples_of)
+
+    def prove_low_degree_batch_dev(self, d_ptr: int, n: int, batch: int, root_of_unity, max_deg_plus_1: int,
+                                   exclude_multiples_of: int) -> list:
+        """The same on device values: vector b is the n elements at d_ptr + 32 n b (not modified)."""
+        return self._prove_batch(self.lib.stark_prove_low_degree_batch_dev, d_ptr, n, batch, root_of_unity,
+                                 max_deg_plus_1, exclude_multiples_of)
+
+    def _prove_batch(self, fn, values, n, batch, root, max_deg_plus_1, excl) -> list:
+        hs = (_vp * max(batch, 1))()
+        self.check(fn(self.h, values, n, batch, _p64(_limbs(root)), max_deg_plus_1, excl, hs), "prove_low_degree_batch")
+        return [FriProofList(self.lib, _vp(hs[b])) for b in range(batch)]
+
 
 class FriProofList:
     """Vec<FriProof<BlakeDigest>> (fri.rs:16-26) held by the library."""
@@ -731,6 +766,53 @@ class MerkleProofInPlace:
         leaves = ctypes.create_string_buffer(max(k * self.leaf_len, 1))
         nodes = ctypes.create_string_buffer(max(k * depth * 32, 1))
         self.ctx.check(self.ctx.lib.stark_merkle_gen_proofs(self.h, arr, k, leaves, nodes), "gen_proofs")
+        lr, nr = leaves.raw, nodes.raw
+        return [Proof(lr[i * self.leaf_len:(i + 1) * self.leaf_len],
+                      [nr[(i * depth + d) * 32:(i * depth + d + 1) * 32] for d in range(depth)]) for i in range(k)]
+
+
+class MerkleForest:
+    """`batch` MerkleProofInPlace trees of n leaves each (merkle_proof_in_place.rs:9-50), built together by
+    one set of launches (stark_merkle_forest_*): tree b's leaves are bytes [b n leaf_len, (b + 1) n leaf_len)
+    of the blob, and its root and paths are those of a MerkleProofInPlace over them."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        h = _vp()
+        ctx.check(ctx.lib.stark_merkle_forest_new(ctx.h, ctypes.byref(h)), "MerkleForest::new")
+        self.h = h
+        self.n = self.leaf_len = self.batch = 0
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.ctx.lib.stark_merkle_forest_free(self.h)
+        except Exception:
+            pass
+
+    def update_bytes(self, blob: bytes, n: int, leaf_len: int, batch: int) -> None:
+        self.ctx.check(self.ctx.lib.stark_merkle_forest_update(self.h, blob, n, leaf_len, batch), "forest update")
+        self.n, self.leaf_len, self.batch = n, leaf_len, batch
+
+    def update_dev(self, d_ptr: int, n: int, leaf_len: int, batch: int, stream: int = 0) -> None:
+        self.ctx.check(self.ctx.lib.stark_merkle_forest_update_dev(self.h, d_ptr, n, leaf_len, batch, stream or None),
+                       "forest update")
+        self.n, self.leaf_len, self.batch = n, leaf_len, batch
+
+    def roots(self) -> list:
+        out = ctypes.create_string_buffer(max(32 * self.batch, 32))
+        self.ctx.check(self.ctx.lib.stark_merkle_forest_roots(self.h, out), "forest roots")
+        return [out.raw[32 * b:32 * b + 32] for b in range(self.batch)]
+
+    def gen_proofs(self, tree: int, indices) -> list:
+        idx = list(indices)
+        k = len(idx)
+        depth = max(self.n.bit_length() - 1, 0)
+        arr = (ctypes.c_size_t * max(k, 1))(*idx)
+        leaves = ctypes.create_string_buffer(max(k * self.leaf_len, 1))
+        nodes = ctypes.create_string_buffer(max(k * depth * 32, 1))
+        self.ctx.check(self.ctx.lib.stark_merkle_forest_gen_proofs(self.h, tree, arr, k, leaves, nodes),
+                       "forest gen_proofs")
         lr, nr = leaves.raw, nodes.raw
         return [Proof(lr[i * self.leaf_len:(i + 1) * self.leaf_len],
                       [nr[(i * depth + d) * 32:(i * depth + d + 1) * 32] for d in range(depth)]) for i in range(k)]
