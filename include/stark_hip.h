@@ -40,8 +40,9 @@ extern "C" {
  * 5: stark_zpoly, stark_lagrange_interp(_domain), stark_mul_polys / stark_div_polys,
  *    stark_ctx_set_public_column_min.
  * 6: stark_eval_poly_multipoint(_dev), stark_ctx_set_multipoint_tree_min, stark_divrem_polys.
- * 7: stark_merkle_forest_*, stark_prove_low_degree_batch(_dev). */
-#define STARK_ABI_VERSION 7u
+ * 7: stark_merkle_forest_*, stark_prove_low_degree_batch(_dev).
+ * 8: stark_prove_r1cs_circuit_batch, stark_ctx_set_prove_batch_limit. */
+#define STARK_ABI_VERSION 8u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -108,6 +109,12 @@ stark_status stark_ctx_set_public_column_min(stark_ctx* ctx, size_t m);
  * pointer may be NULL. */
 stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t* cache_limit,
                               size_t* resident_bytes);
+/* Upper bound on the device bytes a batch's working set may take (stark_prove_r1cs_circuit_batch: its arena, its
+ * three Merkle forests, the batched FRI's forests and columns and the transforms' ping-pong partner; no reference
+ * counterpart).  A larger batch runs as consecutive chunks.  0 restores the default (6 GiB).  A value below one
+ * proof's working set means chunks of one.  The buffers are reused across calls and counted in
+ * stark_ctx_memory's resident_bytes; a cap below what they hold frees them at once. */
+stark_status stark_ctx_set_prove_batch_limit(stark_ctx* ctx, size_t bytes);
 
 /* ---- NTT (packages/fri/src/fft.rs) --------------------------------------- */
 /* best_fft<T>(coefficients: Vec<T>, root_of_unity: &T, log_order_of_root: u32) -> Vec<T>
@@ -411,6 +418,26 @@ stark_status stark_r1cs_circuit_new(stark_ctx* ctx, const uint8_t* r1cs, size_t 
 void stark_r1cs_circuit_free(stark_r1cs_circuit* circuit);
 stark_status stark_prove_r1cs_circuit(stark_ctx* ctx, const stark_r1cs_circuit* circuit, const uint8_t* wtns,
                                       size_t wtns_len, stark_r1cs_proof** out);
+/* prove_with_witness (run.rs:310-452) for `batch` witnesses of one prepared circuit: out[b] is the proof
+ * stark_prove_r1cs_circuit returns for wtns[b], byte for byte.  The batch shares one chain of launches (every
+ * kernel takes the proof as a grid coordinate; the A, main and L trees of the batch are three Merkle forests;
+ * the B linear combinations go through the batched prove_low_degree), in consecutive chunks under
+ * stark_ctx_set_prove_batch_limit.  A caller with one large witness calls stark_prove_r1cs_circuit.
+ * Errors of the call as a whole -- a null ctx, circuit, wtns, wtns_lens or out, a circuit prepared on another
+ * context or for world != 1, batch > 65535 (nothing is read or written then) -- return STARK_ERR_BAD_ARG with
+ * every out[b] NULL; batch == 0 returns STARK_OK and writes nothing.
+ * Errors of one witness are stark_prove_r1cs_circuit's: a null or malformed .wtns, too few values or
+ * witness[0] != 1 give STARK_ERR_BAD_ARG (such a witness never enters the chain), unsatisfied constraints or a
+ * public-wire mismatch give STARK_ERR_CHECK (found by the constraint kernel: the witness runs to the end of the
+ * chain and is dropped after it).  With statuses != NULL the call returns STARK_OK, statuses[b] is that status
+ * and out[b] is non-NULL exactly where statuses[b] == STARK_OK; a failing witness changes no other proof.  With
+ * statuses == NULL the call is all or nothing, as stark_prove_low_degree_batch: the first failing witness's
+ * status is returned and every out[b] is NULL.  Each handle works with the stark_r1cs_proof_* accessors and is
+ * freed with stark_r1cs_proof_free. */
+stark_status stark_prove_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
+                                            const uint8_t* const* wtns, const size_t* wtns_lens, uint32_t batch,
+                                            stark_r1cs_proof** out /* batch handles */,
+                                            stark_status* statuses /* batch entries, or NULL */);
 
 /* ---- multi-GPU four-step NTT building blocks (no reference counterpart;
  * the reference is single-process).  The exchanges are RCCL

@@ -320,6 +320,10 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   for (stark_merkle_tree* t : ctx->fri_trees) stark_merkle_free(t);
   for (stark_merkle_forest* f : ctx->fri_forests) stark_merkle_forest_free(f);
   ctx->fri_forests.clear();
+  for (stark_merkle_forest*& f : ctx->r1cs_forests) {
+    stark_merkle_forest_free(f);
+    f = nullptr;
+  }
   for (void* p : ctx->pinned)
     if (p) hipHostFree(p);
   for (auto& kv : ctx->ext_idx)
@@ -333,7 +337,8 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   if (ctx->aux) hipStreamDestroy(ctx->aux);
   ctx->fri_trees.clear();
   for (DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena, &ctx->trace_raw, &ctx->fri_misc,
-                     &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly}) {
+                     &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly,
+                     &ctx->prove_batch}) {
     if (b->ptr) hipFree(b->ptr);
     if (b->ev) hipEventDestroy(b->ev);
   }
@@ -357,6 +362,27 @@ stark_status stark_ctx_set_public_column_min(stark_ctx* ctx, size_t m) {
   return STARK_OK;
 }
 
+stark_status stark_ctx_set_prove_batch_limit(stark_ctx* ctx, size_t bytes) {
+  if (!ctx) return STARK_ERR_BAD_ARG;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->prove_batch_limit = bytes;
+  // What a batch left behind goes when it is above the new cap (the next batch allocates its chunk's size).
+  const size_t cap = bytes ? bytes : kDefaultProveBatchLimit;
+  size_t held = ctx->prove_batch.ptr ? ctx->prove_batch.bytes : 0;
+  for (const stark_merkle_forest* f : ctx->r1cs_forests) held += forest_device_bytes(f);
+  for (const stark_merkle_forest* f : ctx->fri_forests) held += forest_device_bytes(f);
+  if (held > cap) {
+    STARK_HIP(ctx, hipDeviceSynchronize());  // (a kernel of any stream may still read them)
+    if (ctx->prove_batch.ptr) hipFree(ctx->prove_batch.ptr);
+    ctx->prove_batch.ptr = nullptr;
+    ctx->prove_batch.bytes = 0;
+    ctx->prove_batch.last = nullptr;
+    for (stark_merkle_forest* f : ctx->r1cs_forests) forest_release(f);
+    for (stark_merkle_forest* f : ctx->fri_forests) forest_release(f);
+  }
+  return STARK_OK;
+}
+
 stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t* cache_limit,
                               size_t* resident_bytes) {
   if (!ctx) return STARK_ERR_BAD_ARG;
@@ -365,13 +391,15 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   for (const auto& kv : ctx->tw) total += kv.second->base_bytes;
   for (const DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena,
                           &ctx->trace_raw, &ctx->fri_misc, &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena,
-                          &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly})
+                          &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly, &ctx->prove_batch})
     total += b->ptr ? b->bytes : 0;
   for (const stark_merkle_tree* t : ctx->trees) total += merkle_device_bytes(t);
   for (const stark_merkle_tree* t : ctx->fri_trees) total += merkle_device_bytes(t);
   // prove_low_degree_batch's forests and its staging (pinned slot 5 is host memory the device writes)
   for (const stark_merkle_forest* f : ctx->fri_forests) total += forest_device_bytes(f);
   total += ctx->pinned_bytes[5];
+  // stark_prove_r1cs_circuit_batch's forests (its arena is among the buffers above)
+  for (const stark_merkle_forest* f : ctx->r1cs_forests) total += forest_device_bytes(f);
   if (cached_bytes) *cached_bytes = cached;
   if (cache_limit) *cache_limit = ctx->cache_limit;
   if (resident_bytes) *resident_bytes = total;

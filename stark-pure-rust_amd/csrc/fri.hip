@@ -460,9 +460,36 @@ stark_status fri_prove_device(stark_ctx* ctx, const fe* d_values, size_t n, cons
 // is slot l * batch + b of ctx->fri_batch, written by forest l's root launch.  The openings of all
 // 2 * layers * batch requests come from one gather batch behind the device-derived indices; the roots and the
 // Last values come down behind it into pinned slot 5: one synchronisation for the whole batch.
+// The folded layers of a proof of n values (the loop of fri_check, sizes only).
+static size_t fri_layer_count(size_t n, size_t max_deg_plus_1) {
+  size_t layers = 0;
+  for (size_t m = n, deg = max_deg_plus_1; deg > 16 && m >= 8; m /= 4, deg /= 4) ++layers;
+  return layers;
+}
+
+size_t fri_batch_bytes(size_t n, uint32_t batch, size_t max_deg_plus_1) {
+  const size_t layers = fri_layer_count(n, max_deg_plus_1);
+  size_t bytes = (layers ? layers : 1) * batch * sizeof(fe);  // fri_batch
+  for (size_t l = 0, m = n; l < layers; ++l) {
+    m /= 4;
+    bytes += forest_node_bytes(m, batch) + m * batch * sizeof(fe);
+  }
+  return bytes;
+}
+
+stark_status fri_batch_sx0(stark_ctx* ctx, size_t n, uint32_t batch, const uint64_t root[4], size_t max_deg_plus_1,
+                           uint32_t excl, fe** sx0) {
+  size_t layers = 0;
+  STARK_TRY(fri_check(ctx, n, root, max_deg_plus_1, excl, &layers, nullptr));
+  STARK_TRY(ensure_buf(ctx, ctx->fri_batch, (layers ? layers : 1) * batch * sizeof(fe)));
+  *sx0 = (fe*)ctx->fri_batch.ptr;
+  return STARK_OK;
+}
+
 stark_status fri_prove_batch_device(stark_ctx* ctx, const fe* d_values, size_t n, uint32_t batch,
                                     const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,
-                                    stark_fri_proof** out) {
+                                    stark_fri_proof** out, stark_merkle_forest* forest0,
+                                    const std::function<stark_status()>& mid) {
   const FieldHost& F = FieldHost::get();
   hipStream_t s = ctx->stream;
   size_t layers = 0;
@@ -488,7 +515,9 @@ stark_status fri_prove_batch_device(stark_ctx* ctx, const fe* d_values, size_t n
     STARK_TRY(stark_merkle_forest_new(ctx, &f));
     ctx->fri_forests.push_back(f);
   }
-  std::vector<stark_merkle_forest*>& forests = ctx->fri_forests;
+  // forests[l] commits layer l's values; forest0, when given, is the caller's forest over d_values
+  std::vector<stark_merkle_forest*> forests(ctx->fri_forests.begin(), ctx->fri_forests.begin() + layers + 1);
+  if (forest0) forests[0] = forest0;
 
   fe* d_sx = (fe*)ctx->fri_batch.ptr;
   const fe* cur = d_values;
@@ -500,7 +529,7 @@ stark_status fri_prove_batch_device(stark_ctx* ctx, const fe* d_values, size_t n
   for (size_t layer = 0; layer < layers; ++layer) {
     bool sx_made = true;
     // (every folded layer has m >= 8 values, fri_check: its trees' roots come from the forest's tail launch)
-    if (layer == 0)
+    if (layer == 0 && !forest0)
       STARK_TRY(forest_build(ctx, forests[0], (const uint8_t*)cur, m, 32, batch, s, false, d_sx, &r2, &sx_made));
     const size_t q = m / 4;
     const HostFp zeta = F.pow_u64(w, q);  // w^(n/4)
@@ -568,6 +597,7 @@ stark_status fri_prove_batch_device(stark_ctx* ctx, const fe* d_values, size_t n
     STARK_HIP(ctx, hipGetLastError());
     return STARK_OK;
   };
+  if (mid) STARK_TRY(mid());
   if (layers) STARK_TRY(merkle_gather_batch(ctx, reqs, s, indices));
   else STARK_HIP(ctx, hipStreamSynchronize(s));  // (no gather: the Last values' copy)
 

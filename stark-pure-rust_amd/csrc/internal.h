@@ -147,6 +147,10 @@ constexpr size_t kDefaultVerifyColumnMin = 1024;
 // measured shape (at 8,192 x 8,192 the split Horner still wins, 0.78 ms against 1.86;
 // profiles/multipoint_eval_ab.txt).
 constexpr size_t kDefaultMultipointTreeMin = 65536;
+// Default cap on the device bytes of one chunk of stark_prove_r1cs_circuit_batch (its arena, its three forests
+// and the batched FRI's forests and columns; stark_ctx_set_prove_batch_limit): a larger batch runs as consecutive
+// chunks.  About 20 x precision x 32 B per proof: some 300 proofs at precision 2^15.
+constexpr size_t kDefaultProveBatchLimit = (size_t)6 << 30;
 
 }  // namespace stark
 
@@ -176,8 +180,15 @@ struct stark_ctx {
   // grown across calls, as pinned slot 5 (the batch's roots and Last values).
   std::vector<stark_merkle_forest*> fri_forests;
   stark::DevBuf fri_batch;
-  void* pinned[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // pinned host scratch (ctx_pinned)
-  size_t pinned_bytes[6] = {0, 0, 0, 0, 0, 0};
+  // stark_prove_r1cs_circuit_batch (r1cs.hip prove_r1cs_batch): one chunk's working set, its accumulator, main
+  // and linear-combination forests, and the cap on a chunk's device bytes (0: stark::kDefaultProveBatchLimit);
+  // reused across calls, freed when the cap is lowered below what they hold.
+  stark::DevBuf prove_batch;
+  stark_merkle_forest* r1cs_forests[3] = {nullptr, nullptr, nullptr};
+  size_t prove_batch_limit = 0;
+  // pinned host scratch (ctx_pinned)
+  void* pinned[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t pinned_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
   hipEvent_t staged = nullptr;  // the last DMA out of pinned slot 3 (r1cs_trace_dev.hip staged_upload)
   // A second stream and an event for work the host overlaps with the main stream (the prover's spot-check
   // openings gathered while its FRI layers still run, r1cs.hip); created on first use.
@@ -248,7 +259,9 @@ bool cache_reserve(stark_ctx* ctx, size_t need, bool evict_ext);
 // record-walk tables; slot 3: its upload staging (the raw .r1cs constraint section and witness); slot 4:
 // the prover's small host-made uploads (constraint tables at 0, boundary constants from kPinned4ConstsOff),
 // so they are asynchronous copies (a pageable copy blocks the host).  Slot 5: prove_low_degree_batch's roots
-// and Last values (it grows with the batch; slot 1's fixed layout stays the single proof's).
+// and Last values (it grows with the batch; slot 1's fixed layout stays the single proof's).  Slot 6: the batched
+// prover's transcript heads (kBatchHeadBytes per proof), then its small per-proof uploads and the witnesses' staging.
+constexpr size_t kBatchHeadBytes = 2048;
 constexpr size_t kPinned4ConstsOff = 16384;
 stark_status ctx_pinned(stark_ctx* ctx, int slot, size_t bytes, void** out);
 // Pinned slot 1 (always this size, so no caller's pointer into it moves): [0, 2048) the prover's
@@ -403,11 +416,17 @@ stark_status merkle_gather_batch(stark_ctx* ctx, const std::vector<GatherReq>& r
 // d_leaves + b n leaf_len.  forest_level0 / forest_build(..., level0_ready) as merkle_level0 / merkle_build:
 // tree b's leaf digests go to *level0 + b * *stride_words.  fe_out non-null: the launch that makes the roots
 // writes root b as a field element (RootFe's role, with *r2) to fe_out[b]; *fe_made tells whether one did.
+// plane_stride != 0 (with level0_ready only): tree b's leaves are rows stored as leaf_len / 32 planes of 32 B,
+// plane c of row i at d_leaves + b n leaf_len + c plane_stride + 32 i, as merkle_build's; the gathers open them
+// through tree b's view.
 stark_status forest_level0(stark_ctx* ctx, stark_merkle_forest* f, size_t n, uint32_t batch, uint32_t** level0,
                            size_t* stride_words);
 stark_status forest_build(stark_ctx* ctx, stark_merkle_forest* f, const uint8_t* d_leaves, size_t n, size_t leaf_len,
                           uint32_t batch, hipStream_t stream, bool level0_ready = false, fe* fe_out = nullptr,
-                          const fe* r2 = nullptr, bool* fe_made = nullptr);
+                          const fe* r2 = nullptr, bool* fe_made = nullptr, size_t plane_stride = 0);
+size_t forest_node_bytes(size_t n, uint32_t batch);  // device bytes of such a forest's nodes
+// Frees a forest's device memory; the handle stays usable (the next build allocates again).
+void forest_release(stark_merkle_forest* f);
 // Tree b as the gather code and merkle_root_dev read a tree (owned by the forest, valid until its next build).
 stark_merkle_tree* forest_tree(stark_merkle_forest* f, uint32_t b);
 // Tree 0's nodes as words, with the words from a tree to the next and from a tree's first node to its root.
@@ -624,6 +643,34 @@ struct PreparedCircuit {
   }
 };
 stark_status circuit_build(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len, PreparedCircuit& c);
+// ---- batched proofs of one prepared circuit (stark_prove_r1cs_circuit_batch) ----
+// One witness of a batch, past circuit_witness's host checks: its values (field_size bytes each, value 0 first)
+// and the public wires (canonical limbs, 4 per wire).
+struct BatchWitness {
+  const uint8_t* values = nullptr;
+  uint32_t field_size = 0;
+  std::vector<uint64_t> public_wires;
+};
+// The witness stage's device buffers for `batch` proofs, carved by the prover (r1cs.hip), everything batch-major.
+// sp: proof b's S column at sp + 2 b steps and P at sp + (2 b + 1) steps (the caller zero-fills it: the columns'
+// tails beyond the os trace rows).  h_stage: pinned staging of batch x n_wires x 32 B, the host's at the call.
+struct WitnessBatchBufs {
+  uint8_t* raw = nullptr;                      // batch x n_wires x 32 B
+  fe *wcan = nullptr, *wmont = nullptr;        // batch x n_wires
+  uint32_t *list = nullptr, *count = nullptr;  // batch x n_c long factors, batch counters
+  fe* sp = nullptr;
+  uint64_t steps = 0;
+  uint8_t* h_stage = nullptr;
+};
+// circuit_witness's device part for a batch: one upload, then decode / fill / running sums with a proof coordinate.
+stark_status circuit_witness_batch(stark_ctx* ctx, const PreparedCircuit& c, const BatchWitness* const* w,
+                                   uint32_t batch, const WitnessBatchBufs& bufs, hipStream_t s);
+// mk_r1cs_proof for `batch` witnesses of a circuit prepared for world 1 through one launch chain (r1cs.hip
+// prove_r1cs_batch), in consecutive chunks under the context's prove-batch limit.  statuses[b] / out[b]: proof
+// b's status (STARK_OK, or STARK_ERR_CHECK from the constraint kernel's flags) and handle (null unless STARK_OK).
+// The return value is an error of the chain as a whole (no out[b] is set then).
+stark_status mk_r1cs_proof_batch(stark_ctx* ctx, const PreparedCircuit& c, const BatchWitness* const* w,
+                                 uint32_t batch, stark_r1cs_proof** out, stark_status* statuses);
 // lagrange_interp (fri/src/poly_utils.rs:409-439): coefficients, low degree first (r1cs.hip).
 std::vector<HostFp> lagrange_interp(const std::vector<HostFp>& xs, const std::vector<HostFp>& ys);
 // FRI prover on device values (fri.hip).  fri_enqueue puts every layer on the
@@ -647,7 +694,17 @@ stark_status fri_prove_device(stark_ctx* ctx, const fe* d_values, size_t n, cons
 // and one synchronisation (fri.hip): out[b] = fri_prove_device's proof of vector b; on an error no out[b] is set.
 stark_status fri_prove_batch_device(stark_ctx* ctx, const fe* d_values, size_t n, uint32_t batch,
                                     const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,
-                                    stark_fri_proof** out);
+                                    stark_fri_proof** out, stark_merkle_forest* forest0 = nullptr,
+                                    const std::function<stark_status()>& mid = std::function<stark_status()>());
+// forest0 non-null: the caller's forest over the batch vectors (the batched prover's L forest: layer 0's trees
+// are not hashed twice), whose root launch wrote layer 0's special_x values where fri_batch_sx0 said.  mid
+// (optional) is called once every layer is enqueued and before the openings are gathered: the caller's host
+// work beside the FRI kernels.
+// fri_batch_sx0 sizes ctx->fri_batch for such a call: special_x of (layer 0, proof b) goes to (*sx0)[b].
+stark_status fri_batch_sx0(stark_ctx* ctx, size_t n, uint32_t batch, const uint64_t root[4], size_t max_deg_plus_1,
+                           uint32_t excl, fe** sx0);
+// Device bytes a batched FRI call holds beyond its input: the folded layers' forests and columns.
+size_t fri_batch_bytes(size_t n, uint32_t batch, size_t max_deg_plus_1);
 // prove_low_degree's argument checks alone (fri.hip): the status fri_enqueue returns for these arguments
 // before it enqueues anything.  n_layers / tw_out may be null.
 stark_status fri_check(stark_ctx* ctx, size_t n, const uint64_t root[4], size_t max_deg_plus_1, uint32_t excl,

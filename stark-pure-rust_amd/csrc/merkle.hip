@@ -796,9 +796,12 @@ stark_status forest_level0(stark_ctx* ctx, stark_merkle_forest* f, size_t n, uin
 // (*fe_made tells whether one did: every tree of depth >= 1).
 stark_status forest_build(stark_ctx* ctx, stark_merkle_forest* f, const uint8_t* d_leaves, size_t n, size_t leaf_len,
                           uint32_t batch, hipStream_t stream, bool level0_ready, fe* fe_out, const fe* r2,
-                          bool* fe_made) {
+                          bool* fe_made, size_t plane_stride) {
   if (fe_made) *fe_made = false;
   STARK_TRY(forest_check(n, leaf_len, batch));
+  // Rows stored as planes are never hashed here (forest_build_kernel reads contiguous leaves): their digests
+  // come from the kernel that made the rows.
+  if (plane_stride && (!level0_ready || leaf_len % 32 || plane_stride % 16)) return STARK_ERR_BAD_ARG;
   uint32_t depth = 0;
   while (((size_t)1 << depth) < n) ++depth;
   STARK_TRY(forest_nodes(ctx, f, n, batch));
@@ -865,10 +868,26 @@ stark_status forest_build(stark_ctx* ctx, stark_merkle_forest* f, const uint8_t*
     v.nodes.ptr = (Digest*)f->nodes.ptr + (size_t)b * f->stride;
     v.nodes.bytes = f->stride * sizeof(Digest);
     v.d_leaves = d_leaves + (size_t)b * n * leaf_len;
-    v.plane_stride = 0;
+    v.plane_stride = plane_stride;
     v.built = true;
   }
   return STARK_OK;
+}
+
+size_t forest_node_bytes(size_t n, uint32_t batch) { return (size_t)batch * (2 * n - 1) * sizeof(Digest); }
+
+void forest_release(stark_merkle_forest* f) {
+  if (!f) return;
+  hipSetDevice(f->ctx->device);
+  for (DevBuf* b : {&f->nodes, &f->own_leaves}) {
+    if (b->ptr) hipFree(b->ptr);
+    b->ptr = nullptr;
+    b->bytes = 0;
+    b->last = nullptr;
+  }
+  f->d_leaves = nullptr;
+  f->built = false;
+  f->views.clear();
 }
 
 stark_merkle_tree* forest_tree(stark_merkle_forest* f, uint32_t b) { return &f->views[b]; }

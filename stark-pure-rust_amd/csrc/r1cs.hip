@@ -125,13 +125,28 @@ struct Pow32 {
   fe m[8];
 };
 
+// The trees of a forest as a batched kernel reads their roots: tree b's root words at nodes + b stride + root_at
+// (forest_nodes_dev).
+struct ForestRoots {
+  const uint32_t* nodes;
+  uint64_t stride, root_at;
+  __device__ __forceinline__ const uint32_t* root(uint64_t b) const { return nodes + b * stride + root_at; }
+};
+
 // r = get_random_ff_values(a_root, precision, 3, 0) (utils.rs:272-290):
 // get_pseudorandom_indices(seed, precision, 24, 0) (fri/src/utils.rs:82-109)
 // expands seed || B(seed) || B(B(seed)), reads 24 big-endian words mod
 // precision; each group of 8 is written as big-endian bytes and read back
 // with from_bytes_le (mod p).
+// (BATCH: for proof blockIdx.x of a batch, its accumulator tree's root in the forest `acc` and its transcript
+// tr[blockIdx.x]; the single proof's instantiation is the kernel as it was, `acc` unread.)
+template <bool BATCH>
 __global__ void r1cs_r_kernel(const uint32_t* __restrict__ a_root, uint32_t prec_mask, fe r2, Pow32 p32,
-                              Transcript* __restrict__ tr) {
+                              Transcript* __restrict__ tr, ForestRoots acc) {
+  if constexpr (BATCH) {
+    a_root = acc.root(blockIdx.x);
+    tr += blockIdx.x;
+  }
   __shared__ fe rs[2];
   if (threadIdx.x == 0) {
     uint32_t data[24];
@@ -175,8 +190,8 @@ static_assert(kLincombConsts * 8 <= kKThreads, "r1cs_k_kernel rows");
 // Blake2s(m_root || i) mod p (prove.rs:274-283, utils.rs:25-27, 51-57); then the
 // three per-residue coefficients of L, kx[t] = (k3 + k4 xs_t, k5 + k6 xs_t,
 // k7 + k8 xs_t), so the L kernel needs 8 products per point instead of 14.
-__global__ void r1cs_k_kernel(const uint32_t* __restrict__ m_root, fe r2, fe one_m, XsPowers xs, Pow32 p32,
-                              Transcript* __restrict__ tr) {
+__device__ __forceinline__ void r1cs_k_body(const uint32_t* __restrict__ m_root, const fe& r2, const fe& one_m,
+                                            const XsPowers& xs, const Pow32& p32, Transcript* __restrict__ tr) {
   __shared__ fe ks[11];
   __shared__ fe kx[8][3];
   const uint32_t i = threadIdx.x;
@@ -217,9 +232,35 @@ __global__ void r1cs_k_kernel(const uint32_t* __restrict__ m_root, fe r2, fe one
     db_limbs(fe_mul(canon, p32.m[r]), tr->k_db[c] + 9 * r);
   }
 }
+__global__ void r1cs_k_kernel(const uint32_t* __restrict__ m_root, fe r2, fe one_m, XsPowers xs, Pow32 p32,
+                              Transcript* __restrict__ tr) {
+  r1cs_k_body(m_root, r2, one_m, xs, p32, tr);
+}
+// r1cs_k_kernel for proof blockIdx.x of a batch: its main tree's root, its transcript.
+__global__ void r1cs_k_batch_kernel(ForestRoots mt, fe r2, fe one_m, XsPowers xs, Pow32 p32,
+                                    Transcript* __restrict__ tr) {
+  r1cs_k_body(mt.root(blockIdx.x), r2, one_m, xs, p32, tr + blockIdx.x);
+}
 
 __global__ void r1cs_l_root_kernel(const uint32_t* __restrict__ l_root, Transcript* __restrict__ tr) {
   if (threadIdx.x < 8) tr->roots[2][threadIdx.x] = l_root[threadIdx.x];
+}
+// The same for proof blockIdx.x of a batch (the L forest's root launch writes special_x only).
+__global__ void r1cs_l_root_batch_kernel(ForestRoots lt, Transcript* __restrict__ tr) {
+  if (threadIdx.x < 8) tr[blockIdx.x].roots[2][threadIdx.x] = lt.root(blockIdx.x)[threadIdx.x];
+}
+
+// A batch's transcripts before its chain: everything ahead of c_db zeroed (the constraint flags among it), and
+// the host-built constants (upload_constraint_tables, in tr[0]) copied to every other proof's, so that the
+// batched kernels read tr[b] as the single proof's read tr.
+__global__ void r1cs_tr_init_batch_kernel(Transcript* __restrict__ tr) {
+  constexpr uint32_t kHeadWords = offsetof(Transcript, c_db) / 4, kDbWords = sizeof(Transcript::c_db) / 4;
+  uint32_t* mine = reinterpret_cast<uint32_t*>(tr + blockIdx.x);
+  for (uint32_t k = threadIdx.x; k < kHeadWords; k += blockDim.x) mine[k] = 0;
+  if (blockIdx.x == 0) return;  // (uniform)
+  const uint32_t* src = &tr->c_db[0][0];
+  uint32_t* dst = &tr[blockIdx.x].c_db[0][0];
+  for (uint32_t k = threadIdx.x; k < kDbWords; k += blockDim.x) dst[k] = src[k];
 }
 
 // Montgomery image of g^i from the two-level tables of g.
@@ -232,9 +273,9 @@ __device__ __forceinline__ fe pow_tab(const fe* __restrict__ lo, const fe* __res
 // (utils.rs:254-263).
 // (IDX itself is not written: its extension is the context's shared ext_index_column.)
 // (dig non-null: each 40-B leaf's Blake2s too, the accumulator tree's level 0 (merkle_level0), 8 words.)
-__global__ void r1cs_index_kernel(const uint64_t* __restrict__ perm, uint64_t os, uint64_t steps,
-                                  const fe* __restrict__ w, fe* __restrict__ pidx, uint64_t* __restrict__ acc_leaves,
-                                  uint32_t* __restrict__ dig) {
+__device__ __forceinline__ void r1cs_index_row(const uint64_t* __restrict__ perm, uint64_t os, uint64_t steps,
+                                               const fe* __restrict__ w, fe* __restrict__ pidx,
+                                               uint64_t* __restrict__ acc_leaves, uint32_t* __restrict__ dig) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= steps) return;
   const uint64_t p = i < os ? perm[i] : i;
@@ -258,6 +299,20 @@ __global__ void r1cs_index_kernel(const uint64_t* __restrict__ perm, uint64_t os
     d[0] = make_uint4(h[0], h[1], h[2], h[3]);
     d[1] = make_uint4(h[4], h[5], h[6], h[7]);
   }
+}
+__global__ void r1cs_index_kernel(const uint64_t* __restrict__ perm, uint64_t os, uint64_t steps,
+                                  const fe* __restrict__ w, fe* __restrict__ pidx, uint64_t* __restrict__ acc_leaves,
+                                  uint32_t* __restrict__ dig) {
+  r1cs_index_row(perm, os, steps, w, pidx, acc_leaves, dig);
+}
+// r1cs_index_kernel for proof blockIdx.y of a batch: the circuit's permutation (one copy), the proof's witness
+// column at w + y steps, its PIDX column and leaves likewise, and its tree's level 0 at dig + y dig_stride words.
+__global__ void r1cs_index_batch_kernel(const uint64_t* __restrict__ perm, uint64_t os, uint64_t steps,
+                                        const fe* __restrict__ w, fe* __restrict__ pidx,
+                                        uint64_t* __restrict__ acc_leaves, uint32_t* __restrict__ dig,
+                                        uint64_t dig_stride) {
+  const uint64_t b = blockIdx.y;
+  r1cs_index_row(perm, os, steps, w + b * steps, pidx + b * steps, acc_leaves + b * 5 * steps, dig + b * dig_stride);
 }
 
 // Flag columns F0, F1, F2 (run.rs:283-308) from bytes: dst[f * steps + i] = fb[f * os + i].
@@ -308,10 +363,11 @@ __global__ void r1cs_pack_kernel(PackArgs a) {
 // ext_idx[8 j] = IDX[j] = j and ext_pidx[8 j] = PIDX[j] (the LDE interpolates the step
 // values); with ext_idx == nullptr (distributed prover: the extended columns are
 // sharded) they are taken from the step-domain permutation instead.
-__global__ void r1cs_a_vals_kernel(const fe* __restrict__ ext_idx, const fe* __restrict__ ext_pidx,
-                                   const uint64_t* __restrict__ perm, uint64_t os,
-                                   const fe* __restrict__ w, uint64_t steps, const Transcript* __restrict__ tr, fe mr2,
-                                   fe* __restrict__ nmr_m, fe* __restrict__ dnm_m) {
+__device__ __forceinline__ void r1cs_a_vals_row(const fe* __restrict__ ext_idx, const fe* __restrict__ ext_pidx,
+                                                const uint64_t* __restrict__ perm, uint64_t os,
+                                                const fe* __restrict__ w, uint64_t steps,
+                                                const Transcript* __restrict__ tr, const fe& mr2,
+                                                fe* __restrict__ nmr_m, fe* __restrict__ dnm_m) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= steps) return;
   const fe r0 = tr->r0, r1_m = tr->r1_m, r2_m = tr->r2_m;
@@ -322,6 +378,20 @@ __global__ void r1cs_a_vals_kernel(const fe* __restrict__ ext_idx, const fe* __r
   const fe vd = fe_add(fe_add(r0, fe_mul(xp, r1_m)), rw);
   fe_store(nmr_m + j, fe_mul(vn, mr2));
   fe_store(dnm_m + j, fe_mul(vd, mr2));
+}
+__global__ void r1cs_a_vals_kernel(const fe* __restrict__ ext_idx, const fe* __restrict__ ext_pidx,
+                                   const uint64_t* __restrict__ perm, uint64_t os,
+                                   const fe* __restrict__ w, uint64_t steps, const Transcript* __restrict__ tr, fe mr2,
+                                   fe* __restrict__ nmr_m, fe* __restrict__ dnm_m) {
+  r1cs_a_vals_row(ext_idx, ext_pidx, perm, os, w, steps, tr, mr2, nmr_m, dnm_m);
+}
+// r1cs_a_vals_kernel for proof blockIdx.y of a batch (IDX and PIDX from the step-domain permutation, which is the
+// circuit's): its witness column, transcript and the two product arrays, each `steps` from a proof to the next.
+__global__ void r1cs_a_vals_batch_kernel(const uint64_t* __restrict__ perm, uint64_t os, const fe* __restrict__ w,
+                                         uint64_t steps, const Transcript* __restrict__ tr, fe mr2,
+                                         fe* __restrict__ nmr_m, fe* __restrict__ dnm_m) {
+  const uint64_t b = blockIdx.y;
+  r1cs_a_vals_row(nullptr, nullptr, perm, os, w + b * steps, steps, tr + b, mr2, nmr_m + b * steps, dnm_m + b * steps);
 }
 
 // Inclusive product scan, phase 1: each workgroup scans kScanBlock Montgomery
@@ -335,10 +405,17 @@ struct ScanArrays {
   fe* canon[2];
 };
 
-__global__ __launch_bounds__(256) void scan_block_kernel(ScanArrays a, uint64_t n, fe one_m) {
+// (BATCH: the three scan phases take proof blockIdx.z of a batch, whose arrays are n elements and nb block
+// products behind the previous proof's, so no scan runs across two proofs.)
+template <bool BATCH>
+__global__ __launch_bounds__(256) void scan_block_kernel(ScanArrays a, uint64_t n, fe one_m, uint32_t nb) {
   __shared__ fe part[256];
   fe* __restrict__ v = a.v[blockIdx.y];
   fe* __restrict__ tot = a.tot[blockIdx.y];
+  if constexpr (BATCH) {
+    v += (uint64_t)blockIdx.z * n;
+    tot += (uint64_t)blockIdx.z * nb;
+  }
   const uint64_t base = (uint64_t)blockIdx.x * kScanBlock + 4 * threadIdx.x;
   fe x[4];
   fe acc = one_m;
@@ -367,9 +444,8 @@ __global__ __launch_bounds__(256) void scan_block_kernel(ScanArrays a, uint64_t 
 
 // Phase 2: exclusive scan of the block products (one workgroup; each thread
 // owns a contiguous run).
-__global__ __launch_bounds__(256) void scan_tot_kernel(ScanArrays a, uint32_t nb, fe one_m) {
+__device__ __forceinline__ void scan_tot_body(fe* __restrict__ tot, uint32_t nb, const fe& one_m) {
   __shared__ fe part[256];
-  fe* __restrict__ tot = a.tot[blockIdx.y];
   const uint32_t per = (nb + 255) / 256;
   const uint32_t lo = threadIdx.x * per, hi = lo + per < nb ? lo + per : nb;
   fe acc = one_m;
@@ -396,20 +472,34 @@ __global__ __launch_bounds__(256) void scan_tot_kernel(ScanArrays a, uint32_t nb
     acc = fe_mul(acc, t);
   }
 }
+__global__ __launch_bounds__(256) void scan_tot_kernel(ScanArrays a, uint32_t nb, fe one_m) {
+  scan_tot_body(a.tot[blockIdx.y], nb, one_m);
+}
+// Phase 2 for proof blockIdx.z of a batch (its nb block products behind the previous proof's).
+__global__ __launch_bounds__(256) void scan_tot_batch_kernel(ScanArrays a, uint32_t nb, fe one_m) {
+  scan_tot_body(a.tot[blockIdx.y] + (uint64_t)blockIdx.z * nb, nb, one_m);
+}
 
 // Phase 3: block b (> 0) times the product of blocks before it; also emits
 // the canonical value into `canon` when given.
-__global__ void scan_apply_kernel(ScanArrays a, uint64_t n, fe unit) {
+__device__ __forceinline__ void scan_apply_body(fe* __restrict__ v, const fe* __restrict__ tot,
+                                                fe* __restrict__ canon, uint64_t n, const fe& unit) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  fe* __restrict__ v = a.v[blockIdx.y];
-  const fe* __restrict__ tot = a.tot[blockIdx.y];
-  fe* __restrict__ canon = a.canon[blockIdx.y];
   fe x = fe_load(v + i);
   const uint64_t b = i / kScanBlock;
   if (b) x = fe_mul(x, tot[b]);
   fe_store(v + i, x);
   if (canon) fe_store(canon + i, fe_mul(x, unit));
+}
+__global__ void scan_apply_kernel(ScanArrays a, uint64_t n, fe unit) {
+  scan_apply_body(a.v[blockIdx.y], a.tot[blockIdx.y], a.canon[blockIdx.y], n, unit);
+}
+// Phase 3 for proof blockIdx.z of a batch.
+__global__ void scan_apply_batch_kernel(ScanArrays a, uint64_t n, uint32_t nb, fe unit) {
+  const uint64_t z = blockIdx.z;
+  fe* const canon = a.canon[blockIdx.y];
+  scan_apply_body(a.v[blockIdx.y] + z * n, a.tot[blockIdx.y] + z * nb, canon ? canon + z * n : nullptr, n, unit);
 }
 
 // a_mini[j] = acc_nmr[j] * inv(acc_dnm[j]) (utils.rs:331-336); nmr Montgomery, inv canonical.
@@ -473,6 +563,30 @@ struct ConstraintArgs {
   uint32_t* leaf = nullptr;  // non-null: each row's Blake2s (the main tree's level 0, merkle_level0), 8 words
 };
 
+// A batch's own arguments of the constraint kernel (BATCH): what a proof of the batch has of its own, each at a
+// fixed stride from the previous proof's.  Everything else is read from ConstraintArgs as the single proof
+// reads it: the circuit's columns, the inverses of Zb2 / Zb3, the tables of g2 and every scalar.
+struct ConstraintBatch {
+  const fe *sp, *a_col;  // S at sp + 2 b prec, P at sp + (2 b + 1) prec; A at a_col + b prec
+  const fe* consts;      // boundary_consts of proof b at consts + b consts_stride (interp2 at + n2, interp3 at + 2 n2)
+  uint64_t consts_stride;
+  const fe* i2_col;      // null, or I2's column of proof b at i2_col + b prec
+  fe* rows;              // proof b's 8 planes at rows + 8 b prec
+  Transcript* tr;        // tr[b], whose err takes the proof's flags
+  uint32_t* leaf;        // level 0 of tree b at leaf + b leaf_stride words
+  uint64_t leaf_stride;
+};
+// Proof blockIdx.y's own (BATCH), or the single proof's arguments, read where the kernel reads them (the
+// condition is a template constant: the single proof's instantiation is the kernel as it was, `g` unread).
+#define CK_OWN(single, batched) (BATCH ? (batched) : (single))
+#define CK_TR CK_OWN(a.tr, (const Transcript*)(g.tr + pb))
+#define CK_ERR CK_OWN(a.err, &g.tr[pb].err)
+#define CK_INTERP2 CK_OWN(a.interp2, g.consts + pb * g.consts_stride + a.n2)
+#define CK_INTERP3 CK_OWN(a.interp3, g.consts + pb * g.consts_stride + 2 * (uint64_t)a.n2)
+#define CK_I2COL CK_OWN(a.i2_col, g.i2_col ? g.i2_col + pb * a.prec : (const fe*)nullptr)
+#define CK_ROWS CK_OWN(a.rows, g.rows + 8 * pb * a.prec)
+#define CK_LEAF CK_OWN(a.leaf, g.leaf + pb * g.leaf_stride)
+
 // Q1/Q2/Q3 (utils.rs:181-248, 344-376) -> D1..D3 (utils.rs:379-418), I2/I3
 // evaluations (prove.rs:216-220), B2/B3 (utils.rs:477-524); one main-tree row
 // (prove.rs:235-258) per thread.
@@ -480,12 +594,14 @@ struct ConstraintArgs {
 // compiler's free choice of 180-217 VGPRs two waves per SIMD leave the loads uncovered:
 // 1.94 ms before the digit basis, 1.73 ms with it at this bound, 1.96-1.98 ms at the others,
 // profiles/r05_constraint_db_ab.txt)
-__global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs a) {
+template <bool BATCH>
+__global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs a, ConstraintBatch g) {
+  const uint64_t pb = BATCH ? blockIdx.y : 0;  // the proof
   // The 24 inv(Z) R^k tables in LDS (a lane's t = i mod 8 picks its table): 76 words apart, so the 8
   // tables a wave reads at once start on distinct 4-bank groups.
   __shared__ __attribute__((aligned(16))) uint32_t izt[24 * 76];
   {
-    const uint4* src = reinterpret_cast<const uint4*>(&a.tr->c_db[9][0]);
+    const uint4* src = reinterpret_cast<const uint4*>(&CK_TR->c_db[9][0]);
     for (uint32_t k = threadIdx.x; k < 24 * 18; k += blockDim.x)
       reinterpret_cast<uint4*>(izt)[(k / 18) * 19 + k % 18] = src[k];
     __syncthreads();
@@ -497,14 +613,14 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
   const fe* F0 = a.col[1];
   const fe* F1 = a.col[2];
   const fe* F2 = a.col[3];
-  const fe* S = a.col[4];
-  const fe* Pc = a.col[5];
+  const fe* S = CK_OWN(a.col[4], g.sp + 2 * pb * a.prec);
+  const fe* Pc = CK_OWN(a.col[5], g.sp + (2 * pb + 1) * a.prec);
   const fe* IDX = a.col[6];
   const fe* PIDX = a.col[7];
-  const fe* A = a.col[8];
+  const fe* A = CK_OWN(a.col[8], g.a_col + pb * a.prec);
   const uint64_t prev = (i + n - a.back) & mask;
   const uint64_t gi = a.g_add + (i << a.log_g);  // global evaluation point
-  const fe r0 = a.tr->r0;
+  const fe r0 = CK_TR->r0;
   const fe p = fe_load(Pc + i), s = fe_load(S + i), av = fe_load(A + i);
   const fe p_prev = fe_load(Pc + prev), a_prev = fe_load(A + prev);
   const fe p2 = fe_load(Pc + ((i + a.shift1) & mask)), p3 = fe_load(Pc + ((i + a.shift2) & mask));
@@ -515,9 +631,9 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
   // Products by the proof's constants (r1, r2, R^-1, the a_k below) by the digit basis from the
   // transcript's tables (wave-uniform: scalar loads), each reduced once to canonical: the same values
   // as the Montgomery products by their images, at about half the instructions.
-  const uint32_t* __restrict__ db_r1 = a.tr->r_db[0];
-  const uint32_t* __restrict__ db_r2 = a.tr->r_db[1];
-  const uint32_t* __restrict__ db_rinv = a.tr->c_db[0];
+  const uint32_t* __restrict__ db_r1 = CK_TR->r_db[0];
+  const uint32_t* __restrict__ db_r2 = CK_TR->r_db[1];
+  const uint32_t* __restrict__ db_rinv = CK_TR->c_db[0];
   auto cmul = [](const fe& x, const uint32_t* __restrict__ w) {  // x w mod p, canonical (x < 4p)
     fe y = fe_mul_db(x, w);
     fe_reduce_once(y);
@@ -531,7 +647,7 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
   const fe dnm = fe_add(fe_add(r0, cmul(fe_load(PIDX + i), db_r1)), rs);
   const fe q3 = fe_sub(fe_mul(av, dnm), fe_mul(a_prev, nmr));                                // R^-1
   const uint32_t t = (uint32_t)(gi & 7);
-  if (t == 0 && !(fe_is_zero(q1) && fe_is_zero(q2) && fe_is_zero(q3))) atomicOr(a.err, 1);
+  if (t == 0 && !(fe_is_zero(q1) && fe_is_zero(q2) && fe_is_zero(q3))) atomicOr(CK_ERR, 1);
   auto iz = [&](uint32_t k) {  // the table of inv(Z) R^k at this t
     return static_cast<const uint32_t*>(__builtin_assume_aligned(izt + 76 * (8 * k + t), 16));
   };
@@ -540,14 +656,14 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
   const fe x_m = pow_tab(a.lo, a.hi, a.kb, gi);
   // (Horner from the leading coefficient: the first step's 0 * x + c is c itself)
   fe i2;
-  if (a.i2_col) {  // (uniform)
-    i2 = fe_load(a.i2_col + i);
+  if (CK_I2COL) {  // (uniform)
+    i2 = fe_load(CK_I2COL + i);
   } else {
-    i2 = a.n2 ? a.interp2[a.n2 - 1] : fe_zero();
-    for (uint32_t k = a.n2 ? a.n2 - 1 : 0; k-- > 0;) i2 = fe_add(fe_mul(i2, x_m), a.interp2[k]);
+    i2 = a.n2 ? CK_INTERP2[a.n2 - 1] : fe_zero();
+    for (uint32_t k = a.n2 ? a.n2 - 1 : 0; k-- > 0;) i2 = fe_add(fe_mul(i2, x_m), CK_INTERP2[k]);
   }
-  fe i3 = a.n3 ? a.interp3[a.n3 - 1] : fe_zero();
-  for (uint32_t k = a.n3 ? a.n3 - 1 : 0; k-- > 0;) i3 = fe_add(fe_mul(i3, x_m), a.interp3[k]);
+  fe i3 = a.n3 ? CK_INTERP3[a.n3 - 1] : fe_zero();
+  for (uint32_t k = a.n3 ? a.n3 - 1 : 0; k-- > 0;) i3 = fe_add(fe_mul(i3, x_m), CK_INTERP3[k]);
   fe izb2;
   if (a.tinv) {  // (uniform)
     izb2 = fe_zero();
@@ -556,7 +672,7 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
       const uint64_t m = (i + n - a.pf_shift[k]) & mask;
       root = root || (m == 0 && a.g_add == 0);
       // a_k tinv (a Montgomery image times a canonical a_k: the image of the product), sum in [0, 2p)
-      izb2 = fe_add_raw(izb2, fe_mul_db(fe_load(a.tinv + m), a.tr->c_db[1 + k]));
+      izb2 = fe_add_raw(izb2, fe_mul_db(fe_load(a.tinv + m), CK_TR->c_db[1 + k]));
       fe_csub2p(izb2);
     }
     fe_reduce_once(izb2);
@@ -566,12 +682,12 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
   }
   const fe izb3 = fe_load(a.inv_zb3 + i);
   const fe e2 = fe_sub(s, i2), e3 = fe_sub(av, i3);
-  if (fe_is_zero(izb2) && !fe_is_zero(e2)) atomicOr(a.err, 2);
-  if (fe_is_zero(izb3) && !fe_is_zero(e3)) atomicOr(a.err, 4);
+  if (fe_is_zero(izb2) && !fe_is_zero(e2)) atomicOr(CK_ERR, 2);
+  if (fe_is_zero(izb3) && !fe_is_zero(e3)) atomicOr(CK_ERR, 4);
   const fe b2 = fe_mul(e2, izb2), b3 = fe_mul(e3, izb3);  // (Montgomery images of the inverses: exact)
   // Row i = P|A|S|D1|D2|D3|B2|B3: contiguous (256 B), or column c at rows + c * plane + i
   const uint64_t cs = a.plane ? a.plane : 1;
-  fe* row = a.plane ? a.rows + i : a.rows + 8 * i;
+  fe* row = a.plane ? CK_ROWS + i : CK_ROWS + 8 * i;
   fe_store(row + 0 * cs, p);
   fe_store(row + 1 * cs, av);
   fe_store(row + 2 * cs, s);
@@ -580,7 +696,7 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
   fe_store(row + 5 * cs, d3);
   fe_store(row + 6 * cs, b2);
   fe_store(row + 7 * cs, b3);
-  if (a.leaf) {  // (uniform) the main tree's leaf: Blake2s of the 256-B row, 4 blocks of two values each
+  if (CK_LEAF) {  // (uniform) the main tree's leaf: Blake2s of the 256-B row, 4 blocks of two values each
     uint32_t h[8], m[16];
     b2s_init(h);
     auto block = [&](const fe& x, const fe& y, uint32_t t_bytes, bool last) {
@@ -595,11 +711,19 @@ __global__ __launch_bounds__(256, 3) void r1cs_constraint_kernel(ConstraintArgs 
     block(s, d1, 128, false);
     block(d2, d3, 192, false);
     block(b2, b3, 256, true);
-    uint4* q = reinterpret_cast<uint4*>(a.leaf + 8 * i);
+    uint4* q = reinterpret_cast<uint4*>(CK_LEAF + 8 * i);
     q[0] = make_uint4(h[0], h[1], h[2], h[3]);
     q[1] = make_uint4(h[4], h[5], h[6], h[7]);
   }
 }
+#undef CK_OWN
+#undef CK_TR
+#undef CK_ERR
+#undef CK_INTERP2
+#undef CK_INTERP3
+#undef CK_I2COL
+#undef CK_ROWS
+#undef CK_LEAF
 
 struct LincombArgs {
   const fe* rows;        // the constraint kernel's rows (plane = 0) or columns (plane elements apart)
@@ -614,17 +738,19 @@ struct LincombArgs {
 
 // L = k0 D1 + k1 D2 + k2 D3 + k3 P + k4 P x^steps + k5 B2 + k6 B2 x^steps +
 //     k7 B3 + k8 B3 x^steps + k9 A + k10 S (prove.rs:293-322).
-__global__ __launch_bounds__(256) void r1cs_lincomb_kernel(LincombArgs a) {
+__device__ __forceinline__ void r1cs_lincomb_row(const LincombArgs& a, const fe* __restrict__ rows,
+                                                 fe* __restrict__ out, const Transcript* __restrict__ tr,
+                                                 uint32_t* __restrict__ leaf) {
   // Every product is data x a constant of the proof: the digit-basis product (fe_db.h) from the
   // transcript's tables, staged in LDS; the sum stays in [0, 2p) and is reduced once at the end.
   __shared__ __attribute__((aligned(16))) uint32_t tab[kLincombConsts * 72];
   for (uint32_t k = threadIdx.x; k < kLincombConsts * 18; k += blockDim.x)
-    reinterpret_cast<uint4*>(tab)[k] = reinterpret_cast<const uint4*>(&a.tr->k_db[0][0])[k];
+    reinterpret_cast<uint4*>(tab)[k] = reinterpret_cast<const uint4*>(&tr->k_db[0][0])[k];
   __syncthreads();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.prec) return;
   const uint64_t cs = a.plane ? a.plane : 1;
-  const fe* row = a.plane ? a.rows + i : a.rows + 8 * i;
+  const fe* row = a.plane ? rows + i : rows + 8 * i;
   const uint64_t gi = a.g_add + (i << a.log_g);
   const fe p = fe_load(row + 0 * cs), av = fe_load(row + 1 * cs), s = fe_load(row + 2 * cs),
            d1 = fe_load(row + 3 * cs), d2 = fe_load(row + 4 * cs), d3 = fe_load(row + 5 * cs),
@@ -644,8 +770,8 @@ __global__ __launch_bounds__(256) void r1cs_lincomb_kernel(LincombArgs a) {
   add(acc, fe_mul_db(av, T(3)));          // k9 A
   add(acc, fe_mul_db(s, T(4)));           // k10 S
   fe_reduce_once(acc);
-  fe_store(a.out + i, acc);
-  if (a.leaf) {  // (uniform) the L tree's leaf: Blake2s of the 32-B value
+  fe_store(out + i, acc);
+  if (leaf) {  // (uniform) the L tree's leaf: Blake2s of the 32-B value
     uint32_t h[8], m[16];
     b2s_init(h);
 #pragma unroll
@@ -654,10 +780,19 @@ __global__ __launch_bounds__(256) void r1cs_lincomb_kernel(LincombArgs a) {
       m[8 + w] = 0;
     }
     b2s_compress(h, m, 32, 0, true);
-    uint4* q = reinterpret_cast<uint4*>(a.leaf + 8 * i);
+    uint4* q = reinterpret_cast<uint4*>(leaf + 8 * i);
     q[0] = make_uint4(h[0], h[1], h[2], h[3]);
     q[1] = make_uint4(h[4], h[5], h[6], h[7]);
   }
+}
+__global__ __launch_bounds__(256) void r1cs_lincomb_kernel(LincombArgs a) {
+  r1cs_lincomb_row(a, a.rows, a.out, a.tr, a.leaf);
+}
+// L of proof blockIdx.y of a batch: its rows (8 planes) at a.rows + 8 y prec, its values at a.out + y prec, its
+// transcript a.tr[y] and its tree's level 0 at a.leaf + y leaf_stride words.
+__global__ __launch_bounds__(256) void r1cs_lincomb_batch_kernel(LincombArgs a, uint64_t leaf_stride) {
+  const uint64_t b = blockIdx.y;
+  r1cs_lincomb_row(a, a.rows + 8 * b * a.prec, a.out + b * a.prec, a.tr + b, a.leaf + b * leaf_stride);
 }
 
 // ---- host helpers -----------------------------------------------------------
@@ -817,7 +952,7 @@ static unsigned blocks_for(uint64_t n, unsigned t = 256) { return (unsigned)((n 
 static stark_status product_scan(stark_ctx* ctx, const ScanArrays& a, uint32_t count, uint64_t n, const Mont& mc,
                                  hipStream_t s) {
   const uint32_t nb = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
-  hipLaunchKernelGGL(scan_block_kernel, dim3(nb, count), dim3(256), 0, s, a, n, mc.one);
+  hipLaunchKernelGGL(scan_block_kernel<false>, dim3(nb, count), dim3(256), 0, s, a, n, mc.one, 0u);
   hipLaunchKernelGGL(scan_tot_kernel, dim3(1, count), dim3(256), 0, s, a, nb, mc.one);
   hipLaunchKernelGGL(scan_apply_kernel, dim3(blocks_for(n), count), dim3(256), 0, s, a, n, mc.unit);
   STARK_HIP(ctx, hipGetLastError());
@@ -1313,12 +1448,15 @@ static stark_status stage_buffers(stark_ctx* ctx, const TraceView& v, Stage& st,
 
 // The column route's coefficients, before anything of the proof is enqueued on s (the interpolation's batch
 // inverse takes a host round trip): I2's into pubc + steps and, with_zb2 (no table gives 1 / Zb2), Zb2's
-// times R^-1 into pubc.
+// times R^-1 into pubc.  i2_dst non-null (a batch, whose proofs' I2 coefficients lie back to back; not with_zb2):
+// I2's coefficients, zero-padded to steps, go there and pubc is not touched.
 static stark_status public_coefficients(stark_ctx* ctx, const TraceView& v, const Stage& st, bool with_zb2,
-                                        hipStream_t s) {
+                                        hipStream_t s, fe* i2_dst = nullptr) {
   const uint64_t steps = st.d.steps;
   const size_t n = v.n_pfi;
-  STARK_HIP(ctx, hipMemsetAsync(st.pubc, 0, 2 * steps * sizeof(fe), s));
+  if (i2_dst && with_zb2) return STARK_ERR_BAD_ARG;
+  if (i2_dst) STARK_HIP(ctx, hipMemsetAsync(i2_dst, 0, steps * sizeof(fe), s));
+  else STARK_HIP(ctx, hipMemsetAsync(st.pubc, 0, 2 * steps * sizeof(fe), s));
   DomainHint hint;
   std::vector<uint64_t> staging;
   hint.log_order = st.d.log_steps;
@@ -1330,7 +1468,7 @@ static stark_status public_coefficients(stark_ctx* ctx, const TraceView& v, cons
   STARK_TRY(public_points(ctx, st.roots.g2, st.d.skips, st.d.log_steps, v.public_wires, v.pfi, n,
                           (uint64_t*)(xy + 2 * n), xy, hint, staging, s));
   fe* z = nullptr;  // (the interpolation synchronises s for its batch inverse: staging is free after it)
-  STARK_TRY(lagrange_interp_device(ctx, xy, xy + n, n, st.pubc + steps, mem, s, &hint, &z));
+  STARK_TRY(lagrange_interp_device(ctx, xy, xy + n, n, i2_dst ? i2_dst : st.pubc + steps, mem, s, &hint, &z));
   if (with_zb2) {
     hipLaunchKernelGGL(scale_rinv_kernel, dim3(blocks_for(n + 1)), dim3(256), 0, s, (const fe*)z, (uint64_t)(n + 1),
                        st.pubc);
@@ -1428,8 +1566,8 @@ static stark_status a_chain_enqueue(stark_ctx* ctx, Stage& st, stark_merkle_tree
     STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, s));  // the trace columns, the transcript's zero fill, a_root
     STARK_HIP(ctx, hipStreamWaitEvent(sa, ctx->ev_aux, 0));
   }
-  hipLaunchKernelGGL(r1cs_r_kernel, dim3(1), dim3(64), 0, sa, (const uint32_t*)merkle_root_dev(acc_tree),
-                     (uint32_t)(st.d.prec - 1), st.mc.r2, pow32(), st.d_tr);
+  hipLaunchKernelGGL(r1cs_r_kernel<false>, dim3(1), dim3(64), 0, sa, (const uint32_t*)merkle_root_dev(acc_tree),
+                     (uint32_t)(st.d.prec - 1), st.mc.r2, pow32(), st.d_tr, ForestRoots{});
   STARK_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(r1cs_a_vals_kernel, dim3(blocks_for(steps)), dim3(256), 0, sa, (const fe*)nullptr,
                      (const fe*)nullptr, (const uint64_t*)st.perm, st.d.os, (const fe*)st.wcopy, steps,
@@ -1548,7 +1686,8 @@ static stark_status constraint_args(stark_ctx* ctx, const TraceView& v, const fe
 }
 
 static stark_status constraint_launch(stark_ctx* ctx, const Stage& st, hipStream_t s) {
-  hipLaunchKernelGGL(r1cs_constraint_kernel, dim3(blocks_for(st.d.P)), dim3(256), 0, s, st.ca);
+  hipLaunchKernelGGL(r1cs_constraint_kernel<false>, dim3(blocks_for(st.d.P)), dim3(256), 0, s, st.ca,
+                     ConstraintBatch{});
   STARK_HIP(ctx, hipGetLastError());
   return STARK_OK;
 }
@@ -1740,6 +1879,323 @@ static stark_status prove_r1cs(stark_ctx* ctx, const TraceView& v, const fe* pre
   proof->l_nodes = std::move(l_nodes);
   *out = proof.release();
   return STARK_OK;
+}
+
+// ---- batched proofs of one prepared circuit (stark_prove_r1cs_circuit_batch) --------------------------
+//
+// prove_r1cs with pre != nullptr for B witnesses through one chain of launches: every kernel of the chain takes
+// the proof as a grid coordinate (or runs over the proofs' arrays laid back to back where it is elementwise),
+// every per-proof array is batch-major (proof b at base + b * len), and the three trees of a proof are tree b of
+// three forests.  What stays per witness: the boundary constants and interpolants (host), and on the column
+// route I2's coefficients (one interpolation with its own host round trip per witness, ahead of the chain).
+// The chain itself keeps the single proof's one mid-pipeline round trip (the batch inverse's top level).
+
+// One chunk's working set, carved out of ctx->prove_batch.
+struct BatchBufs {
+  WitnessBatchBufs wb;
+  fe *wcopy, *pidx, *cols_sp, *cols_a, *nmr, *dnm, *tot, *dnm_c, *inv_dnm, *consts, *rows, *lvals;
+  fe *i2coef = nullptr, *i2col = nullptr;  // the column route
+  uint64_t* acc_leaves;
+  Transcript* d_tr;
+};
+
+static void batch_carve(Carve& cv, BatchBufs& bb, const PreparedCircuit& c, const StageDims& d, size_t n_pfi,
+                        bool pub_cols, size_t B) {
+  const uint64_t steps = d.steps, P = d.prec;
+  const size_t nb = (size_t)((steps + kScanBlock - 1) / kScanBlock);
+  cv.add(&bb.wb.raw, B * c.n_wires * 32);
+  cv.add(&bb.wb.wcan, B * c.n_wires);
+  cv.add(&bb.wb.wmont, B * c.n_wires);
+  cv.add(&bb.wb.list, B * c.n_c);
+  cv.add(&bb.wb.count, B);
+  cv.add(&bb.wb.sp, 2 * B * steps);  // S P per proof (then destroyed by their extension)
+  cv.add(&bb.wcopy, B * steps);
+  cv.add(&bb.pidx, B * steps);       // (the index kernel's PIDX column: the circuit's extension is read instead)
+  cv.add(&bb.acc_leaves, 5 * B * steps);
+  cv.add(&bb.cols_sp, 2 * B * P);
+  cv.add(&bb.cols_a, B * P);
+  cv.add(&bb.nmr, B * steps);
+  cv.add(&bb.dnm, B * steps);
+  cv.add(&bb.tot, 2 * B * nb);
+  cv.add(&bb.dnm_c, B * steps);
+  cv.add(&bb.inv_dnm, B * steps);
+  cv.add(&bb.consts, B * (2 * n_pfi + 2));
+  cv.add(&bb.rows, 8 * B * P);
+  cv.add(&bb.lvals, B * P);
+  cv.add(&bb.d_tr, B);
+  if (pub_cols) {
+    cv.add(&bb.i2coef, B * steps);
+    cv.add(&bb.i2col, B * P);
+  }
+}
+
+// The device bytes a chunk of B proofs takes: the arena, the accumulator, main and L forests, the batched FRI's
+// forests and columns, and the NTT's ping-pong partner of the 2 B extended columns.
+static size_t batch_bytes(const PreparedCircuit& c, const StageDims& d, size_t n_pfi, bool pub_cols, uint32_t B) {
+  Carve cv;
+  BatchBufs bb;
+  batch_carve(cv, bb, c, d, n_pfi, pub_cols, B);
+  return cv.off + forest_node_bytes(d.steps, B) + 2 * forest_node_bytes(d.prec, B) +
+         fri_batch_bytes(d.prec, B, d.prec / 4) + 2 * (size_t)B * d.prec * sizeof(fe);
+}
+
+static ForestRoots forest_roots(const stark_merkle_forest* f) {
+  ForestRoots r;
+  r.nodes = forest_nodes_dev(f, &r.stride, &r.root_at);
+  return r;
+}
+
+// The circuit's trace view with one witness' public wires (the sizes and the first uses are every witness').
+static TraceView batch_view(const PreparedCircuit& c, const BatchWitness& w) {
+  TraceView v = c.view(DevTrace());
+  v.public_wires = w.public_wires.data();
+  v.n_public = w.public_wires.size() / 4;
+  return v;
+}
+
+static stark_status prove_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, const BatchWitness* const* w,
+                                     uint32_t B, stark_r1cs_proof** out, stark_status* statuses) {
+  PhaseClock clk("mk_r1cs_proof batch");
+  hipStream_t s = ctx->stream;
+  const fe* const pre = (const fe*)c.lde.ptr;
+  const TraceView v = batch_view(c, *w[0]);
+  Stage st;
+  STARK_TRY(stage_begin(ctx, v, pre, 1, 0, s, st));
+  const StageDims& d = st.d;
+  const uint32_t log_prec = d.log_prec;
+  const uint64_t os = d.os, steps = d.steps, prec = d.prec, skips = d.skips;
+  const size_t n_pfi = v.n_pfi, n_consts = 2 * n_pfi + 2;
+  const uint32_t nb = (uint32_t)((steps + kScanBlock - 1) / kScanBlock);
+  const Mont& mc = st.mc;
+  BatchBufs bb;
+  {
+    Carve cv;
+    batch_carve(cv, bb, c, d, n_pfi, st.pub_cols, B);
+    STARK_TRY(cv.commit(ctx, ctx->prove_batch));
+  }
+  bb.wb.steps = steps;
+  for (stark_merkle_forest*& f : ctx->r1cs_forests)
+    if (!f) STARK_TRY(stark_merkle_forest_new(ctx, &f));
+  stark_merkle_forest *const f_acc = ctx->r1cs_forests[0], *const f_m = ctx->r1cs_forests[1],
+                      *const f_l = ctx->r1cs_forests[2];
+  // Pinned slot 6: the transcript heads, the boundary constants, the witnesses' staging.
+  constexpr size_t kTrHead = offsetof(Transcript, k_db);
+  static_assert(kTrHead <= kBatchHeadBytes, "pinned slot 6 layout");
+  const size_t heads_bytes = (size_t)B * kBatchHeadBytes, consts_bytes = (size_t)B * n_consts * sizeof(fe);
+  uint8_t* pin = nullptr;
+  STARK_TRY(ctx_pinned(ctx, 6, heads_bytes + consts_bytes + (size_t)B * c.n_wires * 32, (void**)&pin));
+  const uint8_t* const h_heads = pin;
+  bb.wb.h_stage = pin + heads_bytes + consts_bytes;
+  {  // per witness: the interpolants through its public wires' values (utils.rs:421-474)
+    fe* const h_consts = (fe*)(pin + heads_bytes);
+    HostFp x_last;
+    for (uint32_t b = 0; b < B; ++b) {
+      const std::vector<fe> h = boundary_consts(st.roots.g2, prec, skips, w[b]->public_wires.data(), v.pfi, n_pfi,
+                                                !st.pub_cols, &x_last);
+      memcpy(h_consts + (size_t)b * n_consts, h.data(), n_consts * sizeof(fe));
+    }
+    STARK_HIP(ctx, hipMemcpyAsync(bb.consts, h_consts, consts_bytes, hipMemcpyHostToDevice, s));
+  }
+  if (st.pub_cols)  // per witness, each with the interpolation's host round trip
+    for (uint32_t b = 0; b < B; ++b)
+      STARK_TRY(public_coefficients(ctx, batch_view(c, *w[b]), st, false, s, bb.i2coef + (size_t)b * steps));
+  // The constraint kernel's shared arguments and the host-built constants (into tr[0], then every transcript's).
+  st.cols = bb.cols_sp;
+  st.consts = bb.consts;
+  st.rows = bb.rows;
+  st.d_tr = bb.d_tr;
+  {
+    const bool pub = st.pub_cols;
+    st.pub_cols = false;  // (I2's columns are extended below, every proof's by one transform)
+    const stark_status cst = constraint_args(ctx, v, pre, st, prec, s);
+    st.pub_cols = pub;
+    STARK_TRY(cst);
+  }
+  hipLaunchKernelGGL(r1cs_tr_init_batch_kernel, dim3(B), dim3(256), 0, s, bb.d_tr);
+  STARK_HIP(ctx, hipGetLastError());
+  // 1. The witness columns, S and P of proof b side by side (their tails beyond os zero).
+  STARK_HIP(ctx, hipMemsetAsync(bb.wb.sp, 0, 2 * (size_t)B * steps * sizeof(fe), s));
+  STARK_TRY(circuit_witness_batch(ctx, c, w, B, bb.wb, s));
+  STARK_HIP(ctx, hipMemcpy2DAsync(bb.wcopy, steps * sizeof(fe), bb.wb.sp, 2 * steps * sizeof(fe), steps * sizeof(fe), B,
+                                  hipMemcpyDeviceToDevice, s));
+  clk.mark("setup + witnesses enqueued");
+  // 2. The accumulator forest -> a_root -> r, per proof.
+  uint32_t* lvl0 = nullptr;
+  size_t lstride = 0;
+  STARK_TRY(forest_level0(ctx, f_acc, steps, B, &lvl0, &lstride));
+  hipLaunchKernelGGL(r1cs_index_batch_kernel, dim3(blocks_for(steps), B), dim3(256), 0, s, c.perm, os, steps,
+                     (const fe*)bb.wcopy, bb.pidx, bb.acc_leaves, lvl0, (uint64_t)lstride);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(forest_build(ctx, f_acc, (const uint8_t*)bb.acc_leaves, steps, 40, B, s, true));
+  // 3. The A chain on the aux stream beside the extension of S and P, as the single proof's; the denominators
+  // of all proofs through one batch inverse (elementwise, 0 -> 0: the concatenation changes no value).
+  STARK_TRY(aux_stream(ctx));
+  const hipStream_t sa = ctx->aux;
+  STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, s));
+  STARK_HIP(ctx, hipStreamWaitEvent(sa, ctx->ev_aux, 0));
+  hipLaunchKernelGGL(r1cs_r_kernel<true>, dim3(B), dim3(64), 0, sa, (const uint32_t*)nullptr, (uint32_t)(prec - 1),
+                     mc.r2, pow32(), bb.d_tr, forest_roots(f_acc));
+  hipLaunchKernelGGL(r1cs_a_vals_batch_kernel, dim3(blocks_for(steps), B), dim3(256), 0, sa, c.perm, os,
+                     (const fe*)bb.wcopy, steps, (const Transcript*)bb.d_tr, mc.r2, bb.nmr, bb.dnm);
+  {
+    const ScanArrays a{{bb.nmr, bb.dnm}, {bb.tot, bb.tot + (size_t)B * nb}, {nullptr, bb.dnm_c}};
+    hipLaunchKernelGGL(scan_block_kernel<true>, dim3(nb, 2, B), dim3(256), 0, sa, a, steps, mc.one, nb);
+    hipLaunchKernelGGL(scan_tot_batch_kernel, dim3(1, 2, B), dim3(256), 0, sa, a, nb, mc.one);
+    hipLaunchKernelGGL(scan_apply_batch_kernel, dim3(blocks_for(steps), 2, B), dim3(256), 0, sa, a, steps, nb, mc.unit);
+  }
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(buf_acquire(ctx, ctx->io2, sa));
+  fe* const top_d = multi_inv_h_top(ctx, 0);
+  if (!top_d) return STARK_ERR_OOM;
+  InvPlan inv_d;
+  STARK_TRY(multi_inv_up(ctx, bb.dnm_c, bb.inv_dnm, (uint64_t)B * steps, sa, ctx->inv_tmp, top_d, inv_d));
+  // 4. S and P of every proof as one batch of 2 B columns.
+  STARK_TRY(extend_columns(ctx, st, bb.wb.sp, 2 * B, bb.cols_sp, s));
+  STARK_HIP(ctx, hipStreamSynchronize(sa));
+  multi_inv_top(inv_d);
+  STARK_TRY(multi_inv_down(ctx, inv_d, sa));
+  hipLaunchKernelGGL(r1cs_a_mini_kernel, dim3(blocks_for((uint64_t)B * steps)), dim3(256), 0, sa, (const fe*)bb.nmr,
+                     (const fe*)bb.inv_dnm, (uint64_t)B * steps, bb.dnm);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(buf_release(ctx, ctx->io2, sa));
+  STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, sa));
+  STARK_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_aux, 0));
+  STARK_TRY(extend_columns(ctx, st, bb.dnm, B, bb.cols_a, s));
+  // 5. The column route: I2 of every proof from its coefficients.
+  if (st.pub_cols)
+    STARK_TRY(coset_forward(ctx, bb.i2coef, B, bb.i2col, d.log_steps, d.log_prec, 0, 0, *st.roots.tw2, *st.roots.twh,
+                            s));
+  // 6. The constraint rows, hashed into level 0 of the main forest (8 planes per proof, as the single tree's).
+  ConstraintBatch g{bb.cols_sp, bb.cols_a, bb.consts,  n_consts, st.pub_cols ? bb.i2col : nullptr,
+                    bb.rows,    bb.d_tr,   nullptr,    0};
+  STARK_TRY(forest_level0(ctx, f_m, prec, B, &g.leaf, &lstride));
+  g.leaf_stride = lstride;
+  hipLaunchKernelGGL(r1cs_constraint_kernel<true>, dim3(blocks_for(prec), B), dim3(256), 0, s, st.ca, g);
+  STARK_HIP(ctx, hipGetLastError());
+  STARK_TRY(forest_build(ctx, f_m, (const uint8_t*)bb.rows, prec, 256, B, s, true, nullptr, nullptr, nullptr,
+                         prec * sizeof(fe)));
+  // 7. k per proof, L hashed into level 0 of the L forest, whose root launch writes FRI layer 0's special_x.
+  hipLaunchKernelGGL(r1cs_k_batch_kernel, dim3(B), dim3(kKThreads), 0, s, forest_roots(f_m), mc.r2, mc.one,
+                     xs_powers(st.roots.g2, steps), pow32(), bb.d_tr);
+  STARK_HIP(ctx, hipGetLastError());
+  LincombArgs la;
+  la.rows = bb.rows;
+  la.plane = prec;
+  la.out = bb.lvals;
+  la.prec = prec;
+  la.g_add = 0;
+  la.log_g = 0;
+  la.tr = bb.d_tr;
+  STARK_TRY(forest_level0(ctx, f_l, prec, B, &la.leaf, &lstride));
+  hipLaunchKernelGGL(r1cs_lincomb_batch_kernel, dim3(blocks_for(prec), B), dim3(256), 0, s, la, (uint64_t)lstride);
+  STARK_HIP(ctx, hipGetLastError());
+  fe* sx0 = nullptr;
+  STARK_TRY(fri_batch_sx0(ctx, prec, B, st.roots.g2c, prec / 4, (uint32_t)skips, &sx0));
+  bool sx_made = false;
+  STARK_TRY(forest_build(ctx, f_l, (const uint8_t*)bb.lvals, prec, 32, B, s, true, sx0, &mc.r2, &sx_made));
+  if (!sx_made) {
+    ctx->last_error = "prove_r1cs_batch: the L forest did not make its roots' field elements";
+    return STARK_ERR_STATE;
+  }
+  hipLaunchKernelGGL(r1cs_l_root_batch_kernel, dim3(B), dim3(64), 0, s, forest_roots(f_l), bb.d_tr);
+  STARK_HIP(ctx, hipGetLastError());
+  // 9. Every proof's transcript head in one copy; an event marks them.
+  STARK_HIP(ctx, hipMemcpy2DAsync(pin, kBatchHeadBytes, bb.d_tr, sizeof(Transcript), kTrHead, B,
+                                  hipMemcpyDeviceToHost, s));
+  STARK_HIP(ctx, hipEventRecord(ctx->ev_aux, s));
+  clk.mark("prover kernels enqueued");
+  // While the FRI layers run: the positions of every proof (prove.rs:337-362) and all their openings as one
+  // gather batch on the second stream.
+  std::vector<std::unique_ptr<stark_r1cs_proof>> proofs(B);
+  std::vector<int> errs(B, 0);
+  std::vector<std::vector<size_t>> positions(B), aug(B);
+  auto spot_checks = [&]() -> stark_status {
+    STARK_HIP(ctx, hipEventSynchronize(ctx->ev_aux));
+    clk.mark("wait for the L roots");
+    std::vector<GatherReq> spot;
+    spot.reserve(2 * (size_t)B);
+    for (uint32_t b = 0; b < B; ++b) {
+      const Transcript* h_tr = reinterpret_cast<const Transcript*>(h_heads + (size_t)b * kBatchHeadBytes);
+      proofs[b] = std::make_unique<stark_r1cs_proof>();
+      stark_r1cs_proof& p = *proofs[b];
+      errs[b] = h_tr->err;
+      memcpy(p.a_root, h_tr->roots[0], 32);
+      memcpy(p.m_root, h_tr->roots[1], 32);
+      memcpy(p.l_root, h_tr->roots[2], 32);
+      uint32_t pos32[kSpotChecks];
+      STARK_TRY(stark_get_pseudorandom_indices(p.l_root, 32, (uint32_t)prec, kSpotChecks, (uint32_t)skips, pos32));
+      positions[b].resize(kSpotChecks);
+      aug[b].resize(4 * kSpotChecks);
+      for (int i = 0; i < kSpotChecks; ++i) {
+        positions[b][i] = pos32[i];
+        spot_rows(pos32[i], os, skips, prec, &aug[b][4 * i]);
+      }
+      p.depth = log_prec;
+      p.l_leaves.resize(32 * kSpotChecks);
+      p.l_nodes.resize((size_t)32 * kSpotChecks * log_prec);
+      p.m_leaves.resize(256 * 4 * kSpotChecks);
+      p.m_nodes.resize((size_t)32 * 4 * kSpotChecks * log_prec);
+      spot.push_back({forest_tree(f_l, b), positions[b].data(), (size_t)kSpotChecks, p.l_leaves.data(),
+                      p.l_nodes.data()});
+      spot.push_back({forest_tree(f_m, b), aug[b].data(), (size_t)4 * kSpotChecks, p.m_leaves.data(),
+                      p.m_nodes.data()});
+    }
+    STARK_TRY(merkle_gather_batch(ctx, spot, ctx->aux));
+    clk.mark("spot-check openings");
+    return STARK_OK;
+  };
+  // 8. prove_low_degree of the B linear combinations on the L forest (prove.rs:367).
+  std::vector<stark_fri_proof*> fri(B, nullptr);
+  STARK_TRY(fri_prove_batch_device(ctx, (const fe*)bb.lvals, prec, B, st.roots.g2c, prec / 4, (uint32_t)skips,
+                                   fri.data(), f_l, spot_checks));
+  clk.mark("FRI wait + indices + gather (last download)");
+  // A witness that failed the constraint kernel's flags ran to the end of the chain and is dropped here.
+  for (uint32_t b = 0; b < B; ++b) {
+    stark_r1cs_proof& p = *proofs[b];
+    p.fri = fri[b];  // owned by the proof from here on
+    if (errs[b]) {
+      statuses[b] = transcript_status(ctx, errs[b]);
+      out[b] = nullptr;
+      continue;
+    }
+    JsonPieces j;
+    stark_proof_json_head(p.m_root, p.l_root, p.a_root, {p.m_leaves, 256, p.m_nodes, (size_t)4 * kSpotChecks, log_prec},
+                          {p.l_leaves, 32, p.l_nodes, (size_t)kSpotChecks, log_prec}, j);
+    fri_proof_json_pieces(p.fri, j);
+    j.text("}");
+    j.render(p.json);
+    statuses[b] = STARK_OK;
+    out[b] = proofs[b].release();
+  }
+  clk.mark("proof JSON");
+  return STARK_OK;
+}
+
+stark_status mk_r1cs_proof_batch(stark_ctx* ctx, const PreparedCircuit& c, const BatchWitness* const* w,
+                                 uint32_t batch, stark_r1cs_proof** out, stark_status* statuses) {
+  if (!ctx || !w || !out || !statuses || !c.lde.ptr || c.world != 1) return STARK_ERR_BAD_ARG;
+  for (uint32_t b = 0; b < batch; ++b) out[b] = nullptr;
+  if (batch == 0) return STARK_OK;
+  // The chunk: as many proofs as stay under the limit by the size of one proof's working set (at least one).
+  const TraceView v = batch_view(c, *w[0]);
+  StageDims d;
+  STARK_TRY(stage_dims(v, 1, 0, d));
+  const size_t one = batch_bytes(c, d, v.n_pfi, public_columns(ctx, v.n_pfi, d.steps), 1);
+  const size_t limit = ctx->prove_batch_limit ? ctx->prove_batch_limit : kDefaultProveBatchLimit;
+  const uint32_t chunk = (uint32_t)std::min<size_t>(batch, std::max<size_t>(1, limit / one));
+  stark_status st = STARK_OK;
+  for (uint32_t b0 = 0; b0 < batch && st == STARK_OK; b0 += chunk) {
+    st = prove_r1cs_batch(ctx, c, w + b0, std::min(chunk, batch - b0), out + b0, statuses + b0);
+    // the chunk's buffers, pinned regions and the witnesses' staging are free for the next one
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == STARK_OK) st = STARK_ERR_HIP;
+    if (ctx->aux && hipStreamSynchronize(ctx->aux) != hipSuccess && st == STARK_OK) st = STARK_ERR_HIP;
+  }
+  if (st != STARK_OK)
+    for (uint32_t b = 0; b < batch; ++b) {
+      stark_r1cs_proof_free(out[b]);
+      out[b] = nullptr;
+    }
+  return st;
 }
 
 // v[i] <- Montgomery image of v[i] (canonical in).

@@ -135,8 +135,9 @@ __global__ void slot_fill_kernel(FillArgs a) {
 // of their additions.  A longer factor (hundreds of terms in pedersen_test, a thousand in bits.r1cs) is
 // listed instead (list / count, the order of no consequence) for running_sum_long_kernel.
 constexpr uint32_t kLongFactor = 32;
-__global__ void running_sum_kernel(const uint32_t* __restrict__ base, uint32_t n_constraints, uint64_t a_len,
-                                   fe* __restrict__ comp, uint32_t* __restrict__ list, uint32_t* __restrict__ count) {
+__device__ __forceinline__ void running_sum_factor(const uint32_t* __restrict__ base, uint32_t n_constraints,
+                                                   uint64_t a_len, fe* __restrict__ comp, uint32_t* __restrict__ list,
+                                                   uint32_t* __restrict__ count) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * (uint64_t)n_constraints) return;
   const uint32_t ci = (uint32_t)(t / 3), f = (uint32_t)(t - 3 * (uint64_t)ci);
@@ -161,14 +162,36 @@ __global__ void running_sum_kernel(const uint32_t* __restrict__ base, uint32_t n
       }
   }
 }
+__global__ void running_sum_kernel(const uint32_t* __restrict__ base, uint32_t n_constraints, uint64_t a_len,
+                                   fe* __restrict__ comp, uint32_t* __restrict__ list, uint32_t* __restrict__ count) {
+  running_sum_factor(base, n_constraints, a_len, comp, list, count);
+}
+// The same for proof blockIdx.y of a batch: its computational column at comp + y comp_stride, its own long-factor
+// list (n_constraints entries) and counter.
+__global__ void running_sum_batch_kernel(const uint32_t* __restrict__ base, uint32_t n_constraints, uint64_t a_len,
+                                         fe* __restrict__ comp, uint64_t comp_stride, uint32_t* __restrict__ list,
+                                         uint32_t* __restrict__ count) {
+  const uint64_t b = blockIdx.y;
+  running_sum_factor(base, n_constraints, a_len, comp + b * comp_stride, list + b * n_constraints, count + b);
+}
 
 // The listed long factors, one wave per factor (the grid's waves stride over the 3 count factors): 64
 // slots at a time, an inclusive scan across the wave (six shifted additions), plus the running total of
 // the slots before.  Field addition is associative, so the sums are the sequential ones.
+// (BATCH: for proof blockIdx.y of a batch, with its own list of n_constraints entries, its counter and its
+// computational column comp_stride behind the previous proof's; gridDim.x workgroups stride over that proof's
+// long factors.  The single proof's instantiation is the kernel as it was, the two last arguments unread.)
+template <bool BATCH>
 __global__ __launch_bounds__(256) void running_sum_long_kernel(const uint32_t* __restrict__ base,
                                                                const uint32_t* __restrict__ list,
                                                                const uint32_t* __restrict__ count, uint64_t a_len,
-                                                               fe* __restrict__ comp) {
+                                                               fe* __restrict__ comp, uint32_t n_constraints,
+                                                               uint64_t comp_stride) {
+  if constexpr (BATCH) {
+    list += (uint64_t)blockIdx.y * n_constraints;
+    count += blockIdx.y;
+    comp += (uint64_t)blockIdx.y * comp_stride;
+  }
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t nw = (gridDim.x * blockDim.x) >> 6;
   const uint32_t items = 3 * *count;
@@ -233,14 +256,30 @@ __global__ void perm_kernel(const uint32_t* __restrict__ keys, const uint32_t* _
 
 // The witness columns of a prepared circuit: the slot fill's witness / term part (run.rs:109-281) from
 // the stored slot wires and coefficients, one thread per slot (running_sum_kernel follows).
-__global__ void wit_fill_kernel(uint64_t n_slots, const uint32_t* __restrict__ slot_wire, const fe* __restrict__ coef,
-                                const fe* __restrict__ wcan, const fe* __restrict__ wmont, fe* __restrict__ wit,
-                                fe* __restrict__ comp) {
+__device__ __forceinline__ void wit_fill_slot(uint64_t n_slots, const uint32_t* __restrict__ slot_wire,
+                                              const fe* __restrict__ coef, const fe* __restrict__ wcan,
+                                              const fe* __restrict__ wmont, fe* __restrict__ wit,
+                                              fe* __restrict__ comp) {
   const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= n_slots) return;
   const uint32_t wire = slot_wire[slot];
   fe_store(comp + slot, fe_mul(fe_load(coef + slot), fe_load(wmont + wire)));  // padding slots: coefficient 0
   fe_store(wit + slot, fe_load(wcan + wire));
+}
+__global__ void wit_fill_kernel(uint64_t n_slots, const uint32_t* __restrict__ slot_wire, const fe* __restrict__ coef,
+                                const fe* __restrict__ wcan, const fe* __restrict__ wmont, fe* __restrict__ wit,
+                                fe* __restrict__ comp) {
+  wit_fill_slot(n_slots, slot_wire, coef, wcan, wmont, wit, comp);
+}
+// The same for proof blockIdx.y of a batch: the circuit's slot wires and coefficients (one copy), the proof's
+// decoded witness at wcan / wmont + y n_wires, its S column at sp + 2 y steps and its P column `steps` after it.
+__global__ void wit_fill_batch_kernel(uint64_t n_slots, const uint32_t* __restrict__ slot_wire,
+                                      const fe* __restrict__ coef, const fe* __restrict__ wcan,
+                                      const fe* __restrict__ wmont, uint64_t n_wires, fe* __restrict__ sp,
+                                      uint64_t steps) {
+  const uint64_t b = blockIdx.y;
+  fe* const wit = sp + 2 * b * steps;
+  wit_fill_slot(n_slots, slot_wire, coef, wcan + b * n_wires, wmont + b * n_wires, wit, wit + steps);
 }
 
 unsigned blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
@@ -611,8 +650,8 @@ stark_status r1cs_trace_device(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_
   hipLaunchKernelGGL(slot_fill_kernel, dim3(blocks(std::max<uint64_t>(3 * a_len, n_public))), dim3(256), 0, s, fa);
   hipLaunchKernelGGL(running_sum_kernel, dim3(blocks(3 * (uint64_t)n_c)), dim3(256), 0, s, fa.base, n_c, a_len,
                      fa.comp, long_list, long_cnt);
-  hipLaunchKernelGGL(running_sum_long_kernel, dim3(kLongSumBlocks), dim3(256), 0, s, fa.base,
-                     (const uint32_t*)long_list, (const uint32_t*)long_cnt, a_len, fa.comp);
+  hipLaunchKernelGGL(running_sum_long_kernel<false>, dim3(kLongSumBlocks), dim3(256), 0, s, fa.base,
+                     (const uint32_t*)long_list, (const uint32_t*)long_cnt, a_len, fa.comp, 0u, (uint64_t)0);
   hipLaunchKernelGGL(flags_kernel, dim3(blocks(n_c)), dim3(256), 0, s, (const uint32_t*)(A + o_base), n_c, a_len,
                      flags + os, flags + 2 * os);
   STARK_HIP(ctx, hipGetLastError());
@@ -843,8 +882,9 @@ static stark_status circuit_witness(stark_ctx* ctx, const PreparedCircuit& c, co
                      (const fe*)(A + o_wcan), (const fe*)(A + o_wmont), (fe*)(A + o_wit), (fe*)(A + o_comp));
   hipLaunchKernelGGL(running_sum_kernel, dim3(blocks(3 * (uint64_t)c.n_c)), dim3(256), 0, s, c.base, c.n_c, c.a_len,
                      (fe*)(A + o_comp), (uint32_t*)(A + o_long), (uint32_t*)(A + o_cnt));
-  hipLaunchKernelGGL(running_sum_long_kernel, dim3(kLongSumBlocks), dim3(256), 0, s, c.base,
-                     (const uint32_t*)(A + o_long), (const uint32_t*)(A + o_cnt), c.a_len, (fe*)(A + o_comp));
+  hipLaunchKernelGGL(running_sum_long_kernel<false>, dim3(kLongSumBlocks), dim3(256), 0, s, c.base,
+                     (const uint32_t*)(A + o_long), (const uint32_t*)(A + o_cnt), c.a_len, (fe*)(A + o_comp), 0u,
+                     (uint64_t)0);
   STARK_HIP(ctx, hipGetLastError());
   out->os = c.os;
   out->n_constraints = c.n_c;
@@ -852,6 +892,67 @@ static stark_status circuit_witness(stark_ctx* ctx, const PreparedCircuit& c, co
   out->wit = (fe*)(A + o_wit);
   out->comp = (fe*)(A + o_comp);
   out->public_first_indices = c.pfi;
+  return STARK_OK;
+}
+
+// circuit_witness's host checks alone (what rejects a witness before anything is enqueued), with the public wires.
+static stark_status witness_host_checks(const PreparedCircuit& c, const uint8_t* wtns, size_t wtns_len,
+                                        BatchWitness* out) {
+  const FieldHost& F = FieldHost::get();
+  WtnsHeader wh;
+  STARK_TRY(parse_wtns_header(wtns, wtns_len, &wh));
+  if (wh.n_wit < c.n_wires || c.n_public > wh.n_wit) return STARK_ERR_BAD_ARG;
+  const uint8_t* wv = wtns + wh.values_off;
+  const HostFp w0 = F.reduce_bytes_le(wv, wh.field_size);  // witness[0] == 1 (run.rs:358)
+  if (!(w0.v[0] == 1 && w0.v[1] == 0 && w0.v[2] == 0 && w0.v[3] == 0)) return STARK_ERR_BAD_ARG;
+  out->values = wv;
+  out->field_size = wh.field_size;
+  out->public_wires.resize(4 * c.n_public);
+  for (size_t i = 0; i < c.n_public; ++i) {
+    const HostFp v = F.reduce_bytes_le(wv + i * wh.field_size, wh.field_size);
+    memcpy(&out->public_wires[4 * i], v.v, 32);
+  }
+  return STARK_OK;
+}
+
+// The witness columns of `batch` proofs.  Only the circuit's n_wires values of a witness are read (the slot
+// wires are below n_wires), widened to 32 B in the pinned staging so that one copy and one decode launch over
+// the concatenation serve every proof; the fill and the running sums take the proof as grid.y.
+stark_status circuit_witness_batch(stark_ctx* ctx, const PreparedCircuit& c, const BatchWitness* const* w,
+                                   uint32_t batch, const WitnessBatchBufs& bufs, hipStream_t s) {
+  const FieldHost& F = FieldHost::get();
+  const size_t n_wires = c.n_wires, per = n_wires * 32;
+  const unsigned T = (size_t)batch * per > ((size_t)1 << 20) ? std::min<unsigned>(host_threads(), batch) : 1;
+  host_parallel(T, [&](unsigned t) {
+    for (uint32_t b = t; b < batch; b += T) {
+      uint8_t* dst = bufs.h_stage + (size_t)b * per;
+      const uint32_t fs = w[b]->field_size;
+      if (fs == 32) {
+        memcpy(dst, w[b]->values, per);
+      } else {
+        memset(dst, 0, per);
+        for (size_t i = 0; i < n_wires; ++i) memcpy(dst + 32 * i, w[b]->values + i * fs, fs);
+      }
+    }
+  });
+  STARK_HIP(ctx, hipMemcpyAsync(bufs.raw, bufs.h_stage, (size_t)batch * per, hipMemcpyHostToDevice, s));
+  STARK_HIP(ctx, hipMemsetAsync(bufs.count, 0, (size_t)batch * 4, s));
+  uint64_t one_r[4];
+  memcpy(one_r, F.one().v, 32);
+  const uint64_t n_all = (uint64_t)batch * n_wires;
+  hipLaunchKernelGGL(wit_decode_kernel, dim3(blocks(n_all)), dim3(256), 0, s, (const uint32_t*)bufs.raw, 8u, n_all,
+                     to_dev(F.from_canonical(one_r)), bufs.wcan, bufs.wmont, (uint32_t*)nullptr);
+  hipLaunchKernelGGL(wit_fill_batch_kernel, dim3(blocks(3 * c.a_len), batch), dim3(256), 0, s, 3 * c.a_len,
+                     c.slot_wire, c.coef, (const fe*)bufs.wcan, (const fe*)bufs.wmont, (uint64_t)n_wires, bufs.sp,
+                     bufs.steps);
+  fe* const comp = bufs.sp + bufs.steps;
+  hipLaunchKernelGGL(running_sum_batch_kernel, dim3(blocks(3 * (uint64_t)c.n_c), batch), dim3(256), 0, s, c.base,
+                     c.n_c, c.a_len, comp, 2 * bufs.steps, bufs.list, bufs.count);
+  // (a proof's long factors are few: the workgroups that stride over them shrink with the batch)
+  const unsigned long_blocks = std::max(8u, kLongSumBlocks / batch);
+  hipLaunchKernelGGL(running_sum_long_kernel<true>, dim3(long_blocks, batch), dim3(256), 0, s, c.base,
+                     (const uint32_t*)bufs.list, (const uint32_t*)bufs.count, c.a_len, comp, c.n_c, 2 * bufs.steps);
+  STARK_HIP(ctx, hipGetLastError());
   return STARK_OK;
 }
 
@@ -903,6 +1004,56 @@ stark_status stark_prove_r1cs_circuit(stark_ctx* ctx, const stark_r1cs_circuit* 
   if (st != STARK_OK) return st;
   if (!c.lde.ptr) return STARK_ERR_BAD_ARG;
   return mk_r1cs_proof_view(ctx, c.view(dt), (const fe*)c.lde.ptr, out);
+}
+
+stark_status stark_prove_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
+                                            const uint8_t* const* wtns, const size_t* wtns_lens, uint32_t batch,
+                                            stark_r1cs_proof** out, stark_status* statuses) {
+  if (!ctx || !circuit || !wtns || !wtns_lens || !out) return STARK_ERR_BAD_ARG;
+  if (batch > 65535) return STARK_ERR_BAD_ARG;  // (a forest's tree coordinate is grid.y; nothing is read or written)
+  for (uint32_t b = 0; b < batch; ++b) out[b] = nullptr;
+  if (circuit->ctx != ctx || circuit->c.world != 1 || !circuit->c.lde.ptr) return STARK_ERR_BAD_ARG;
+  if (batch == 0) return STARK_OK;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const PreparedCircuit& c = circuit->c;
+  // The host checks of every witness first: a witness they reject never enters the chain.  Without `statuses`
+  // the call reports its first failing witness, so nothing behind a rejected one needs proving.
+  std::vector<BatchWitness> ws(batch);
+  std::vector<stark_status> sts(batch, STARK_OK);
+  uint32_t upto = batch;
+  for (uint32_t b = 0; b < batch; ++b) {
+    sts[b] = wtns[b] ? witness_host_checks(c, wtns[b], wtns_lens[b], &ws[b]) : STARK_ERR_BAD_ARG;
+    if (sts[b] != STARK_OK && !statuses) {
+      upto = b;
+      break;
+    }
+  }
+  std::vector<const BatchWitness*> live;
+  std::vector<uint32_t> at;
+  for (uint32_t b = 0; b < upto; ++b)
+    if (sts[b] == STARK_OK) {
+      live.push_back(&ws[b]);
+      at.push_back(b);
+    }
+  std::vector<stark_r1cs_proof*> got(live.size(), nullptr);
+  std::vector<stark_status> got_st(live.size(), STARK_OK);
+  if (!live.empty()) {
+    const stark_status st = mk_r1cs_proof_batch(ctx, c, live.data(), (uint32_t)live.size(), got.data(), got_st.data());
+    hipStreamSynchronize(ctx->stream);
+    if (st != STARK_OK) return st;
+  }
+  for (size_t k = 0; k < live.size(); ++k) sts[at[k]] = got_st[k];
+  if (!statuses) {  // all or nothing
+    for (uint32_t b = 0; b < batch; ++b)
+      if (sts[b] != STARK_OK) {
+        for (stark_r1cs_proof* p : got) stark_r1cs_proof_free(p);
+        return sts[b];
+      }
+  }
+  for (size_t k = 0; k < live.size(); ++k) out[at[k]] = got[k];
+  if (statuses)
+    for (uint32_t b = 0; b < batch; ++b) statuses[b] = sts[b];
+  return STARK_OK;
 }
 
 stark_status stark_dprove_circuit_new(stark_ctx* ctx, uint32_t world, uint32_t rank, const uint8_t* r1cs,

@@ -56,6 +56,7 @@ _SIGNATURES = {
     "stark_ctx_set_cache_limit": ([_vp, ctypes.c_size_t], ctypes.c_int),
     "stark_ctx_set_public_column_min": ([_vp, ctypes.c_size_t], ctypes.c_int),
     "stark_ctx_memory": ([_vp, _szp, _szp, _szp], ctypes.c_int),
+    "stark_ctx_set_prove_batch_limit": ([_vp, ctypes.c_size_t], ctypes.c_int),
     "stark_best_fft": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p], ctypes.c_int),
     "stark_inv_best_fft": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p], ctypes.c_int),
     "stark_fft_in_place": ([_vp, _u64p, _u64p, ctypes.c_uint32, ctypes.c_int], ctypes.c_int),
@@ -153,6 +154,8 @@ _SIGNATURES = {
     "stark_r1cs_circuit_new": ([_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_r1cs_circuit_free": ([_vp], None),
     "stark_prove_r1cs_circuit": ([_vp, _vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_prove_r1cs_circuit_batch": ([_vp, _vp, ctypes.POINTER(ctypes.c_char_p), _szp, ctypes.c_uint32,
+                                        ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
     "stark_dprove_circuit_new": ([_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
                                   ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_dprove_begin_circuit": ([_vp, _vp, ctypes.c_char_p, ctypes.c_size_t, _vp, ctypes.POINTER(_vp)],
@@ -334,6 +337,11 @@ class Context:
         """From how many public points proofs and verifications take the column route (I2 and Zb2 extended
         from their coefficients); 0 = the default, PUBLIC_COLUMN_NEVER = never.  Same proofs either way."""
         self.check(self.lib.stark_ctx_set_public_column_min(self.h, int(m)), "set_public_column_min")
+
+    def set_prove_batch_limit(self, nbytes: int):
+        """Cap on the device bytes of one chunk of R1csCircuit.prove_batch (a larger batch runs as consecutive
+        chunks); 0 = the default.  A cap below what the batch buffers hold frees them at once."""
+        self.check(self.lib.stark_ctx_set_prove_batch_limit(self.h, int(nbytes)), "set_prove_batch_limit")
 
     def memory(self) -> dict:
         """{'cached': bytes of cached tables, 'cache_limit': their cap, 'resident': all device bytes held}."""

@@ -5,6 +5,7 @@
     prove_with_witness(ctx, r1cs, wtns)   run.rs:310-452
     prove_with_file_path(ctx, ...)     run.rs:528-554 (writes the proof JSON)
     R1csCircuit(ctx, r1cs).prove(wtns) the same proofs, circuit-only work done once
+    R1csCircuit.prove_batch(wtns_list) the same proofs for many witnesses through one launch chain
     StarkProof                         utils.rs:122-130 (serde_json text + roots)
 
 Everything runs in libstark_hip.so; there is no CPU fallback.
@@ -199,6 +200,37 @@ class R1csCircuit:
         self.ctx.check(self.ctx.lib.stark_prove_r1cs_circuit(self.ctx.h, self.h, wtns, len(wtns), ctypes.byref(h)),
                        "prove_r1cs_circuit")
         return StarkProof(self.ctx.lib, h)
+
+    def prove_batch(self, wtns_list, strict: bool = True) -> list:
+        """prove(w) for every w of wtns_list through one chain of launches (stark_prove_r1cs_circuit_batch): the
+        same proofs, byte for byte.  strict: the first failing witness raises StarkError (its .index tells
+        which).  Otherwise the list holds a StarkError instance (with .index) in the place of each failed
+        witness and a StarkProof everywhere else."""
+        ws = [None if w is None else bytes(w) for w in wtns_list]
+        n = len(ws)
+        if n == 0:
+            return []
+        lib = self.ctx.lib
+        ptrs = (ctypes.c_char_p * n)(*ws)
+        lens = (ctypes.c_size_t * n)(*[0 if w is None else len(w) for w in ws])
+        hs = (_vp * n)()
+        sts = (ctypes.c_int * n)()
+        self.ctx.check(lib.stark_prove_r1cs_circuit_batch(self.ctx.h, self.h, ptrs, lens, n, hs, sts),
+                       "prove_r1cs_circuit_batch")
+        out = []
+        for b in range(n):
+            if sts[b] == 0:
+                out.append(StarkProof(lib, _vp(hs[b])))
+            else:
+                detail = lib.stark_ctx_last_error(self.ctx.h).decode() if sts[b] == 8 else ""
+                e = StarkError(sts[b], f"prove_r1cs_circuit_batch, witness {b}", detail)
+                e.index = b
+                out.append(e)
+        if strict:
+            for x in out:
+                if isinstance(x, StarkError):
+                    raise x
+        return out
 
 
 def prove_with_file_path(ctx: Context, r1cs_file_path: str, witness_file_path: str, proof_json_path: str) -> None:
