@@ -41,8 +41,9 @@ extern "C" {
  *    stark_ctx_set_public_column_min.
  * 6: stark_eval_poly_multipoint(_dev), stark_ctx_set_multipoint_tree_min, stark_divrem_polys.
  * 7: stark_merkle_forest_*, stark_prove_low_degree_batch(_dev).
- * 8: stark_prove_r1cs_circuit_batch, stark_ctx_set_prove_batch_limit. */
-#define STARK_ABI_VERSION 8u
+ * 8: stark_prove_r1cs_circuit_batch, stark_ctx_set_prove_batch_limit.
+ * 9: stark_verify_r1cs_circuit_batch, stark_ctx_set_verify_batch_limit, STARK_VERIFY_FAIL_*. */
+#define STARK_ABI_VERSION 9u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -115,6 +116,12 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
  * proof's working set means chunks of one.  The buffers are reused across calls and counted in
  * stark_ctx_memory's resident_bytes; a cap below what they hold frees them at once. */
 stark_status stark_ctx_set_prove_batch_limit(stark_ctx* ctx, size_t bytes);
+/* Upper bound on the bytes one chunk of stark_verify_r1cs_circuit_batch stages: its proofs' packed openings
+ * with their records, once in pinned host memory and once on the device (no reference counterpart).  A larger
+ * batch runs as consecutive chunks.  0 restores the default (256 MiB).  A value below one proof's bytes means
+ * chunks of one.  The buffers are reused across calls and counted in stark_ctx_memory's resident_bytes; a cap
+ * below what they hold frees them at once. */
+stark_status stark_ctx_set_verify_batch_limit(stark_ctx* ctx, size_t bytes);
 
 /* ---- NTT (packages/fri/src/fft.rs) --------------------------------------- */
 /* best_fft<T>(coefficients: Vec<T>, root_of_unity: &T, log_order_of_root: u32) -> Vec<T>
@@ -672,7 +679,8 @@ stark_status stark_ctx_synchronize(stark_ctx* ctx);
  * (an invalid proof).  STARK_ERR_BAD_ARG: malformed input, including a proof JSON that
  * serde_json would not parse as StarkProof<BlakeDigest>.  The circuit-only extensions
  * (K, F0-F2, IDX, PIDX over the precision domain) come from a prepared circuit on the
- * GPU; the Merkle paths, FRI layer checks and the 80 spot checks run on the host. */
+ * GPU; the Merkle paths, FRI layer checks and the 80 spot checks of one proof run on the host,
+ * those of a batch of proofs on the GPU (the batched call below). */
 
 /* verify_low_degree_proof (fri.rs:226-242): layers[0..n_layers) are the Middle layers,
  * last_values[i] (last_lens[i] bytes) the Last layer's values; root_of_unity canonical. */
@@ -685,6 +693,34 @@ stark_status stark_verify_low_degree_proof(const uint8_t merkle_root[32], const 
 stark_status stark_verify_r1cs_circuit(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
                                        const uint8_t* public_wires, size_t n_public, const char* proof_json,
                                        size_t json_len);
+/* verify_with_witness (run.rs:454-526, verify.rs:13-258, fri.rs:226-404) for `batch` proofs of one prepared
+ * circuit (world 1, of this context): statuses[b] is what stark_verify_r1cs_circuit returns for public_wires[b]
+ * (n_public x 32 B each) and proof_json[b] (json_lens[b] bytes), always.  The reference has no batched
+ * verifier: a proof whose structure is what the circuit implies (the Middle layers then one Last, 40 column and
+ * 160 polynomial openings per layer, 320 main and 80 L openings, leaves of 32 / 32 / 256 / 32 B, one node per
+ * tree level) is checked on the GPU -- every Merkle path (Proof::validate, merkle_tree.rs:25-43), every FRI row
+ * (fri.rs:318-345) and every spot check (verify.rs:185-254) of the whole chunk by three launches, the circuit's
+ * columns read in place -- with the Last layers (fri.rs:346-403) on the host workers beside them; any other
+ * proof goes through the single-proof verifier.
+ * Whole-call errors (STARK_ERR_BAD_ARG, nothing read or written, no device call): a null ctx, circuit,
+ * public_wires, proof_json or json_lens, a circuit of another context or of world != 1, n_public == 0,
+ * batch > 65535.  batch == 0 is then STARK_OK (the handles are not read).  With statuses != NULL the call returns STARK_OK (or a device
+ * error) and statuses[b] holds proof b's status (a null entry or unparsable text: STARK_ERR_BAD_ARG); with
+ * statuses == NULL it returns the first status in batch order that is not STARK_OK.  One proof's failure
+ * changes no other proof's status.
+ * reasons (optional) is a diagnostic with no reference counterpart: 0 where statuses[b] is STARK_OK, else the
+ * OR of every failed class of checks, each evaluated independently of the others. */
+#define STARK_VERIFY_FAIL_PUBLIC_ONE 0x01u    /* public_wires[0] != 1 (run.rs:480); alone, nothing else is run */
+#define STARK_VERIFY_FAIL_FRI_PATHS 0x02u     /* a column or polynomial opening of a FRI layer (fri.rs:288-316) */
+#define STARK_VERIFY_FAIL_FRI_ROWS 0x04u      /* a row's cubic against its column value (fri.rs:318-345) */
+#define STARK_VERIFY_FAIL_FRI_LAST 0x08u      /* the Last layer's root or degree (fri.rs:346-403) */
+#define STARK_VERIFY_FAIL_OPENING_PATHS 0x10u /* one of the 320 main or 80 L openings (verify.rs:86-118) */
+#define STARK_VERIFY_FAIL_SPOT 0x20u          /* one of a position's six equalities (verify.rs:185-254) */
+#define STARK_VERIFY_FAIL_SINGLE 0x40u        /* refused by the single-proof verifier; alone */
+stark_status stark_verify_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
+                                             const uint8_t* const* public_wires, size_t n_public,
+                                             const char* const* proof_json, const size_t* json_lens,
+                                             uint32_t batch, stark_status* statuses, uint32_t* reasons);
 /* The same from the .r1cs bytes (read_r1cs + verify_with_witness). */
 stark_status stark_verify_r1cs_bytes(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len,
                                      const uint8_t* public_wires, size_t n_public, const char* proof_json,

@@ -338,7 +338,7 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   ctx->fri_trees.clear();
   for (DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena, &ctx->trace_raw, &ctx->fri_misc,
                      &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly,
-                     &ctx->prove_batch}) {
+                     &ctx->prove_batch, &ctx->verify_batch}) {
     if (b->ptr) hipFree(b->ptr);
     if (b->ev) hipEventDestroy(b->ev);
   }
@@ -383,6 +383,26 @@ stark_status stark_ctx_set_prove_batch_limit(stark_ctx* ctx, size_t bytes) {
   return STARK_OK;
 }
 
+stark_status stark_ctx_set_verify_batch_limit(stark_ctx* ctx, size_t bytes) {
+  if (!ctx) return STARK_ERR_BAD_ARG;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->verify_batch_limit = bytes;
+  // What a batch left behind goes when it is above the new cap (the next batch allocates its chunk's size).
+  const size_t cap = bytes ? bytes : kDefaultVerifyBatchLimit;
+  const size_t held = std::max(ctx->verify_batch.ptr ? ctx->verify_batch.bytes : 0, ctx->pinned_bytes[7]);
+  if (held > cap) {
+    STARK_HIP(ctx, hipDeviceSynchronize());  // (a kernel or copy of any stream may still use them)
+    if (ctx->verify_batch.ptr) hipFree(ctx->verify_batch.ptr);
+    ctx->verify_batch.ptr = nullptr;
+    ctx->verify_batch.bytes = 0;
+    ctx->verify_batch.last = nullptr;
+    if (ctx->pinned[7]) hipHostFree(ctx->pinned[7]);
+    ctx->pinned[7] = nullptr;
+    ctx->pinned_bytes[7] = 0;
+  }
+  return STARK_OK;
+}
+
 stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t* cache_limit,
                               size_t* resident_bytes) {
   if (!ctx) return STARK_ERR_BAD_ARG;
@@ -391,13 +411,16 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   for (const auto& kv : ctx->tw) total += kv.second->base_bytes;
   for (const DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena,
                           &ctx->trace_raw, &ctx->fri_misc, &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena,
-                          &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly, &ctx->prove_batch})
+                          &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly, &ctx->prove_batch,
+                          &ctx->verify_batch})
     total += b->ptr ? b->bytes : 0;
   for (const stark_merkle_tree* t : ctx->trees) total += merkle_device_bytes(t);
   for (const stark_merkle_tree* t : ctx->fri_trees) total += merkle_device_bytes(t);
   // prove_low_degree_batch's forests and its staging (pinned slot 5 is host memory the device writes)
   for (const stark_merkle_forest* f : ctx->fri_forests) total += forest_device_bytes(f);
   total += ctx->pinned_bytes[5];
+  // stark_verify_r1cs_circuit_batch's staging (its device image is among the buffers above)
+  total += ctx->pinned_bytes[7];
   // stark_prove_r1cs_circuit_batch's forests (its arena is among the buffers above)
   for (const stark_merkle_forest* f : ctx->r1cs_forests) total += forest_device_bytes(f);
   if (cached_bytes) *cached_bytes = cached;

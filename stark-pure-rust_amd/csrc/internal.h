@@ -151,6 +151,11 @@ constexpr size_t kDefaultMultipointTreeMin = 65536;
 // and the batched FRI's forests and columns; stark_ctx_set_prove_batch_limit): a larger batch runs as consecutive
 // chunks.  About 20 x precision x 32 B per proof: some 300 proofs at precision 2^15.
 constexpr size_t kDefaultProveBatchLimit = (size_t)6 << 30;
+// Default cap on the bytes one chunk of stark_verify_r1cs_circuit_batch stages (the packed openings with their
+// records, in pinned host memory and again on the device; stark_ctx_set_verify_batch_limit): a larger batch runs
+// as consecutive chunks.  A proof stages its leaves, a 32-B node per tree level of each path and 32 B per record
+// (DESIGN.md 5.6.1): 0.9 MB at precision 2^18, some 280 proofs per chunk.
+constexpr size_t kDefaultVerifyBatchLimit = (size_t)256 << 20;
 
 }  // namespace stark
 
@@ -186,9 +191,14 @@ struct stark_ctx {
   stark::DevBuf prove_batch;
   stark_merkle_forest* r1cs_forests[3] = {nullptr, nullptr, nullptr};
   size_t prove_batch_limit = 0;
+  // stark_verify_r1cs_circuit_batch (verify_batch.hip): one chunk's device image (boundary points, records, packed
+  // openings, ok bytes), staged in pinned slot 7, and the cap on a chunk's staged bytes (0:
+  // stark::kDefaultVerifyBatchLimit); reused across calls, freed when the cap is lowered below what they hold.
+  stark::DevBuf verify_batch;
+  size_t verify_batch_limit = 0;
   // pinned host scratch (ctx_pinned)
-  void* pinned[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t pinned_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
+  void* pinned[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t pinned_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hipEvent_t staged = nullptr;  // the last DMA out of pinned slot 3 (r1cs_trace_dev.hip staged_upload)
   // A second stream and an event for work the host overlaps with the main stream (the prover's spot-check
   // openings gathered while its FRI layers still run, r1cs.hip); created on first use.
@@ -261,6 +271,7 @@ bool cache_reserve(stark_ctx* ctx, size_t need, bool evict_ext);
 // so they are asynchronous copies (a pageable copy blocks the host).  Slot 5: prove_low_degree_batch's roots
 // and Last values (it grows with the batch; slot 1's fixed layout stays the single proof's).  Slot 6: the batched
 // prover's transcript heads (kBatchHeadBytes per proof), then its small per-proof uploads and the witnesses' staging.
+// Slot 7: the batched verifier's staging (the image of ctx->verify_batch, its ok bytes included).
 constexpr size_t kBatchHeadBytes = 2048;
 constexpr size_t kPinned4ConstsOff = 16384;
 stark_status ctx_pinned(stark_ctx* ctx, int slot, size_t bytes, void** out);

@@ -26,46 +26,19 @@
 #include "host_json.h"
 #include "blake2s.h"
 #include "host_b2s.h"
+#include "verify_in.h"
 
 namespace stark {
+
+bool sampler(const uint8_t seed[32], size_t modulus, uint32_t count, uint32_t excl, std::vector<size_t>& out) {
+  if (modulus > 0xFFFFFFFFull) return false;
+  std::vector<uint32_t> v(count);
+  if (stark_get_pseudorandom_indices(seed, 32, (uint32_t)modulus, count, excl, v.data()) != STARK_OK) return false;
+  out.assign(v.begin(), v.end());
+  return true;
+}
+
 namespace {
-
-// ---- the proof, as serde_json writes it (utils.rs:122-130, merkle_tree.rs:14-18, fri.rs:16-26) ----
-
-// Bytes held elsewhere: the proof text's arena (ProofIn::arena) or the caller's arrays.  A parsed proof
-// makes no allocation per opening (freeing ~3,600 small vectors written by 16 threads took ~0.27 ms of a
-// 1.35 ms pedersen verify, profiles/r05_verify_phases.txt).
-struct Bytes {
-  const uint8_t* p = nullptr;
-  size_t n = 0;
-  const uint8_t* data() const { return p; }
-  size_t size() const { return n; }
-  const uint8_t* begin() const { return p; }
-  const uint8_t* end() const { return p + n; }
-};
-
-struct Branch {  // commitment::merkle_tree::Proof
-  Bytes leaf;
-  Bytes nodes;  // 32 B each, leaf -> root
-};
-
-struct FriIn {  // FriProof::Middle { root2, column_branches, poly_branches } | Last { last }
-  bool last = false;
-  uint8_t root2[32] = {0};
-  std::vector<Branch> col, poly;
-  std::vector<std::vector<uint8_t>> last_vals;
-};
-
-struct ProofIn {
-  uint8_t m_root[32], l_root[32], a_root[32];
-  std::vector<Branch> main, lcomb;
-  std::vector<FriIn> fri;
-  // The openings' bytes: the opening whose text starts at offset t is written from arena + t / 2 (a
-  // number takes two characters at least, so an opening's bytes end before its text's end / 2 and
-  // openings side by side never overlap; pre_parse_branches bounds each parallel parse by the next
-  // candidate's start, so a candidate nested inside another opening cannot write into it).
-  std::unique_ptr<uint8_t[]> arena;
-};
 
 class Json;
 
@@ -581,13 +554,6 @@ void paths_check(const std::vector<PathCheck>& v, std::vector<uint8_t>& ok) {
     if (lo < hi && lo < v.size()) b2s_paths(jobs.data() + lo, std::min(hi, v.size()) - lo, ok.data() + lo);
   });
 }
-bool sampler(const uint8_t seed[32], size_t modulus, uint32_t count, uint32_t excl, std::vector<size_t>& out) {
-  if (modulus > 0xFFFFFFFFull) return false;
-  std::vector<uint32_t> v(count);
-  if (stark_get_pseudorandom_indices(seed, 32, (uint32_t)modulus, count, excl, v.data()) != STARK_OK) return false;
-  out.assign(v.begin(), v.end());
-  return true;
-}
 
 // verify_low_degree_proof_rec (fri.rs:244-404).
 // `extra` (optional): more path checks to run in the same parallel pass as the layers' (the verifier's
@@ -712,6 +678,20 @@ stark_status verify_fri(const uint8_t merkle_root_in[32], HostFp root, const std
   }
   const FriIn& last = proof.back();
   if (!last.last) return STARK_ERR_BAD_ARG;  // "The last element of FRI proofs must be FriProof::Last."
+  return fri_last_check(last, m_root, root, max_deg_plus_1, excl);
+}
+
+uint32_t log2_ceil_ref(size_t v) {  // log2_ceil (r1cs-stark/src/utils.rs:14-23)
+  uint32_t l = 1;
+  for (size_t t = v; t > 1; t /= 2) ++l;
+  return l;
+}
+
+}  // namespace
+
+stark_status fri_last_check(const FriIn& last, const uint8_t m_root[32], const HostFp& root, size_t max_deg_plus_1,
+                            uint32_t excl) {
+  const FieldHost& F = FieldHost::get();
   if (max_deg_plus_1 < 16 / 2) return STARK_ERR_CHECK;           // MIN_DEG_DIRECT_CHECKING / 2 (fri.rs:348-351)
   const size_t n = last.last_vals.size();
   if (n <= max_deg_plus_1) return STARK_ERR_CHECK;               // fri.rs:359
@@ -748,18 +728,89 @@ stark_status verify_fri(const uint8_t merkle_root_in[32], HostFp root, const std
   return STARK_OK;
 }
 
-uint32_t log2_ceil_ref(size_t v) {  // log2_ceil (r1cs-stark/src/utils.rs:14-23)
-  uint32_t l = 1;
-  for (size_t t = v; t > 1; t /= 2) ++l;
-  return l;
+VerifyDomain verify_domain(size_t os) {
+  const FieldHost& F = FieldHost::get();
+  VerifyDomain d;
+  const uint32_t log_steps = log2_ceil_ref(os - 1);
+  d.steps = std::max<uint64_t>((uint64_t)1 << log_steps, 8);
+  d.prec = 8 * d.steps;
+  d.skips = 8;
+  uint64_t pm1[4];  // g2 = 7^((p-1)/precision) (verify.rs:55-63)
+  memcpy(pm1, FieldHost::kP, 32);
+  pm1[0] -= 1;
+  for (uint64_t t = d.prec; t > 1; t /= 2)
+    for (int l = 0; l < 4; ++l) pm1[l] = (pm1[l] >> 1) | (l < 3 ? pm1[l + 1] << 63 : 0);
+  d.g2 = F.pow(F.from_u64(7), pm1, 4);
+  return d;
 }
 
-}  // namespace
+std::vector<HostFp> verify_boundary_points(const PreparedCircuit& c, const VerifyDomain& d) {
+  const FieldHost& F = FieldHost::get();
+  std::vector<HostFp> bx;
+  for (size_t i = 0; i + 1 < c.pfi.size(); i += 2) bx.push_back(F.pow_u64(d.g2, d.skips * c.pfi[i + 1]));
+  return bx;
+}
 
-// verify_r1cs_proof (verify.rs:13-258) for a prepared circuit; `pub_bytes` holds the public
-// wires as 32-byte little-endian integers (from_bytes_le, run.rs:477-480).
-static stark_status verify_r1cs(stark_ctx* ctx, const PreparedCircuit& c, const uint8_t* pub_bytes, size_t n_public,
-                                const ProofIn& pr) {
+stark_status verify_interp2(stark_ctx* ctx, const PreparedCircuit& c, const std::vector<HostFp>& pub,
+                            const VerifyDomain& d, const std::vector<HostFp>& bx, std::vector<HostFp>& interp2) {
+  const FieldHost& F = FieldHost::get();
+  const uint64_t steps = d.steps, skips = d.skips;
+  const HostFp& g2 = d.g2;
+  // Boundary interpolants (verify.rs:151-155, utils.rs:421-474) over Zb2's points.
+  std::vector<HostFp> by;
+  for (size_t i = 0; i + 1 < c.pfi.size(); i += 2) by.push_back(pub[c.pfi[i]]);
+  // (from the context's threshold on, by the subproduct tree on the GPU: x_k = g1^(w_k), g1 = g2^skips)
+  const size_t n_b = bx.size(), col_min = ctx->public_column_min ? ctx->public_column_min : kDefaultVerifyColumnMin;
+  if (n_b > 0 && n_b >= col_min && n_b < steps) {
+    std::vector<uint64_t> exps(n_b), ys(4 * n_b), out(4 * n_b), g1c(4);
+    for (size_t i = 0; i < n_b; ++i) {
+      exps[i] = c.pfi[2 * i + 1];
+      F.to_canonical(by[i], &ys[4 * i]);
+    }
+    F.to_canonical(F.pow_u64(g2, skips), g1c.data());
+    uint32_t log_order = 0;
+    while (((uint64_t)1 << log_order) < steps) ++log_order;
+    STARK_TRY(stark_lagrange_interp_domain(ctx, g1c.data(), log_order, exps.data(), ys.data(), n_b, out.data()));
+    interp2.resize(n_b);
+    for (size_t i = 0; i < n_b; ++i) interp2[i] = F.from_canonical(&out[4 * i]);
+  } else {
+    interp2 = lagrange_interp(bx, by);
+  }
+  return STARK_OK;
+}
+
+bool verify_challenges(const ProofIn& pr, uint64_t prec, HostFp r[3], HostFp kk[11]) {
+  const FieldHost& F = FieldHost::get();
+  // r (utils.rs:272-290) and k (verify.rs:164-173).
+  {
+    std::vector<size_t> rnd;
+    if (!sampler(pr.a_root, prec, 24, 0, rnd)) return false;
+    for (int k = 0; k < 3; ++k) {
+      uint8_t be[32];
+      for (int i = 0; i < 8; ++i) {
+        const uint32_t v = (uint32_t)rnd[8 * k + i];
+        be[4 * i] = (uint8_t)(v >> 24);
+        be[4 * i + 1] = (uint8_t)(v >> 16);
+        be[4 * i + 2] = (uint8_t)(v >> 8);
+        be[4 * i + 3] = (uint8_t)v;
+      }
+      r[k] = F.from_bytes_le(be, 32);
+    }
+  }
+  kk[0] = F.one();
+  for (int i = 1; i < 11; ++i) {
+    uint8_t msg[33], h[32], le[32];
+    memcpy(msg, pr.m_root, 32);
+    msg[32] = (uint8_t)i;
+    b2s_host(msg, 33, h);
+    for (int b = 0; b < 32; ++b) le[b] = h[31 - b];  // from_str of the big-endian integer
+    kk[i] = F.from_bytes_le(le, 32);
+  }
+  return true;
+}
+
+stark_status verify_r1cs(stark_ctx* ctx, const PreparedCircuit& c, const uint8_t* pub_bytes, size_t n_public,
+                         const ProofIn& pr) {
   const FieldHost& F = FieldHost::get();
   PhaseClock clk("verify_r1cs_proof");
   if (c.world != 1) return STARK_ERR_BAD_ARG;
@@ -771,14 +822,9 @@ static stark_status verify_r1cs(stark_ctx* ctx, const PreparedCircuit& c, const 
   for (size_t i = 0; i < c.n_public; ++i) pub[i] = F.from_bytes_le(pub_bytes + 32 * i, 32);
   if (!FieldHost::eq(pub[0], F.one())) return STARK_ERR_CHECK;  // run.rs:480
   const size_t os = c.os;
-  const uint32_t log_steps = log2_ceil_ref(os - 1);
-  const uint64_t steps = std::max<uint64_t>((uint64_t)1 << log_steps, 8), prec = 8 * steps, skips = 8;
-  uint64_t pm1[4];  // g2 = 7^((p-1)/precision) (verify.rs:55-63)
-  memcpy(pm1, FieldHost::kP, 32);
-  pm1[0] -= 1;
-  for (uint64_t t = prec; t > 1; t /= 2)
-    for (int l = 0; l < 4; ++l) pm1[l] = (pm1[l] >> 1) | (l < 3 ? pm1[l + 1] << 63 : 0);
-  const HostFp g2 = F.pow(F.from_u64(7), pm1, 4);
+  const VerifyDomain dom = verify_domain(os);
+  const uint64_t steps = dom.steps, prec = dom.prec, skips = dom.skips;
+  const HostFp g2 = dom.g2;
   // FRI on the linear combination (verify.rs:80-84), then the spot checks' openings (verify.rs:86-118).
   // Every Merkle path of both -- the FRI layers', the 320 main and 80 L openings -- is checked in one
   // parallel pass inside verify_fri; the outcomes are reported in the reference's order.
@@ -831,59 +877,13 @@ static stark_status verify_r1cs(stark_ctx* ctx, const PreparedCircuit& c, const 
     while (FieldHost::ge_p(v.v)) FieldHost::sub_p_in_place(v.v);
     return k < 4 && c.with_zb ? v : F.from_canonical(v.v);  // a Montgomery image's bits are the HostFp itself
   };
-  // Boundary interpolants (verify.rs:151-155, utils.rs:421-474) and Zb2's points.
-  std::vector<HostFp> bx, by;
-  for (size_t i = 0; i + 1 < c.pfi.size(); i += 2) {
-    bx.push_back(F.pow_u64(g2, skips * c.pfi[i + 1]));
-    by.push_back(pub[c.pfi[i]]);
-  }
-  // (from the context's threshold on, by the subproduct tree on the GPU: x_k = g1^(w_k), g1 = g2^skips)
+  const std::vector<HostFp> bx = verify_boundary_points(c, dom);
   std::vector<HostFp> interp2;
-  const size_t n_b = bx.size(), col_min = ctx->public_column_min ? ctx->public_column_min : kDefaultVerifyColumnMin;
-  if (n_b > 0 && n_b >= col_min && n_b < steps) {
-    std::vector<uint64_t> exps(n_b), ys(4 * n_b), out(4 * n_b), g1c(4);
-    for (size_t i = 0; i < n_b; ++i) {
-      exps[i] = c.pfi[2 * i + 1];
-      F.to_canonical(by[i], &ys[4 * i]);
-    }
-    F.to_canonical(F.pow_u64(g2, skips), g1c.data());
-    uint32_t log_order = 0;
-    while (((uint64_t)1 << log_order) < steps) ++log_order;
-    STARK_TRY(stark_lagrange_interp_domain(ctx, g1c.data(), log_order, exps.data(), ys.data(), n_b, out.data()));
-    interp2.resize(n_b);
-    for (size_t i = 0; i < n_b; ++i) interp2[i] = F.from_canonical(&out[4 * i]);
-  } else {
-    interp2 = lagrange_interp(bx, by);
-  }
+  STARK_TRY(verify_interp2(ctx, c, pub, dom, bx, interp2));
   const HostFp x_last = F.pow_u64(g2, (steps - 1) * skips);
   const std::vector<HostFp> interp3 = lagrange_interp({x_last}, {F.one()});
-  // r (utils.rs:272-290) and k (verify.rs:164-173).
-  HostFp r[3];
-  {
-    std::vector<size_t> rnd;
-    if (!sampler(pr.a_root, prec, 24, 0, rnd)) return STARK_ERR_CHECK;
-    for (int k = 0; k < 3; ++k) {
-      uint8_t be[32];
-      for (int i = 0; i < 8; ++i) {
-        const uint32_t v = (uint32_t)rnd[8 * k + i];
-        be[4 * i] = (uint8_t)(v >> 24);
-        be[4 * i + 1] = (uint8_t)(v >> 16);
-        be[4 * i + 2] = (uint8_t)(v >> 8);
-        be[4 * i + 3] = (uint8_t)v;
-      }
-      r[k] = F.from_bytes_le(be, 32);
-    }
-  }
-  HostFp kk[11];
-  kk[0] = F.one();
-  for (int i = 1; i < 11; ++i) {
-    uint8_t msg[33], h[32], le[32];
-    memcpy(msg, pr.m_root, 32);
-    msg[32] = (uint8_t)i;
-    b2s_host(msg, 33, h);
-    for (int b = 0; b < 32; ++b) le[b] = h[31 - b];  // from_str of the big-endian integer
-    kk[i] = F.from_bytes_le(le, 32);
-  }
+  HostFp r[3], kk[11];
+  if (!verify_challenges(pr, prec, r, kk)) return STARK_ERR_CHECK;
   // The 80 spot checks are independent: checked on the host workers.
   auto spot = [&](size_t i) -> bool {
     const HostFp x = F.pow_u64(g2, positions[i]);
@@ -976,11 +976,16 @@ stark_status stark_verify_low_degree_proof(const uint8_t merkle_root[32], const 
 
 namespace stark {
 // The StarkProof JSON into pr; false where serde_json::from_reader fails (run.rs:579).
-static bool read_proof(const char* proof_json, size_t json_len, ProofIn& pr) {
-  PhaseClock clk("verify: read proof");
-  PreBranches pre;
+bool read_proof(const char* proof_json, size_t json_len, ProofIn& pr, bool serial) {
   pr.arena.reset(new uint8_t[json_len / 2 + 64]);
   uint8_t* const arena_end = pr.arena.get() + json_len / 2 + 64;
+  if (serial) {  // every opening by the sequential reader itself (what the pre-parse's result is defined as)
+    Json j(proof_json, json_len, nullptr, pr.arena.get(), arena_end);
+    j.stark_proof(pr);
+    return j.ok;
+  }
+  PhaseClock clk("verify: read proof");
+  PreBranches pre;
   pre_parse_branches(proof_json, json_len, pre, pr.arena.get(), arena_end);
   clk.mark("openings parsed (parallel)");
   Json j(proof_json, json_len, &pre, pr.arena.get(), arena_end);

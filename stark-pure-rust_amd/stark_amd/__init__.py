@@ -184,6 +184,10 @@ _SIGNATURES = {
                                        ctypes.c_uint32], ctypes.c_int),
     "stark_verify_r1cs_circuit": ([_vp, _vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t],
                                   ctypes.c_int),
+    "stark_verify_r1cs_circuit_batch": ([_vp, _vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
+                                         ctypes.POINTER(ctypes.c_char_p), _szp, ctypes.c_uint32,
+                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "stark_ctx_set_verify_batch_limit": ([_vp, ctypes.c_size_t], ctypes.c_int),
     "stark_verify_r1cs_bytes": ([_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                  ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
     "stark_group_create": ([ctypes.POINTER(ctypes.c_int), ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
@@ -342,6 +346,12 @@ class Context:
         """Cap on the device bytes of one chunk of R1csCircuit.prove_batch (a larger batch runs as consecutive
         chunks); 0 = the default.  A cap below what the batch buffers hold frees them at once."""
         self.check(self.lib.stark_ctx_set_prove_batch_limit(self.h, int(nbytes)), "set_prove_batch_limit")
+
+    def set_verify_batch_limit(self, nbytes: int):
+        """Cap on the bytes one chunk of R1csCircuit.verify_batch stages, in pinned host memory and on the device
+        (a larger batch runs as consecutive chunks); 0 = the default.  A cap below what the buffers hold frees
+        them at once."""
+        self.check(self.lib.stark_ctx_set_verify_batch_limit(self.h, int(nbytes)), "set_verify_batch_limit")
 
     def memory(self) -> dict:
         """{'cached': bytes of cached tables, 'cache_limit': their cap, 'resident': all device bytes held}."""

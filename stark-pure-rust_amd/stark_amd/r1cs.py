@@ -233,6 +233,13 @@ class R1csCircuit:
         return out
 
 
+    def verify_batch(self, public_wires_list, proofs) -> list:
+        """[(status, reasons)] of verify_circuit(public_wires, proof) for every pair, checked on the GPU through
+        one chain of launches (stark_amd.verify.verify_circuit_batch)."""
+        from .verify import verify_circuit_batch
+        return verify_circuit_batch(self.ctx, self, public_wires_list, proofs)
+
+
 def prove_with_file_path(ctx: Context, r1cs_file_path: str, witness_file_path: str, proof_json_path: str) -> None:
     """run.rs:528-554."""
     with open(r1cs_file_path, "rb") as f:

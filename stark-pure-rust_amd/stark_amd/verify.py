@@ -108,6 +108,37 @@ def verify_circuit(ctx: Context, circuit, public_wires, proof) -> bool:
     return _result(rc, "verify_with_witness")
 
 
+# stark_verify_r1cs_circuit_batch's reasons (include/stark_hip.h STARK_VERIFY_FAIL_*)
+FAIL_PUBLIC_ONE, FAIL_FRI_PATHS, FAIL_FRI_ROWS, FAIL_FRI_LAST = 0x01, 0x02, 0x04, 0x08
+FAIL_OPENING_PATHS, FAIL_SPOT, FAIL_SINGLE = 0x10, 0x20, 0x40
+
+
+def verify_circuit_batch(ctx: Context, circuit, public_wires_list, proofs) -> list:
+    """verify_circuit for every (public_wires, proof) pair through one chain of launches
+    (stark_verify_r1cs_circuit_batch): [(status, reasons)] per proof -- status 0 = verifies, 8 = invalid,
+    3 = malformed (or None in place of an entry); reasons = the OR of the failed FAIL_* classes.  Raises only
+    for an error of the call as a whole."""
+    n = len(proofs)
+    if len(public_wires_list) != n:
+        raise StarkError(3, "verify_circuit_batch", "one set of public wires per proof expected")
+    if n == 0:
+        return []
+    pubs = [None if w is None else _wire_bytes(w) for w in public_wires_list]
+    n_public = {len(p) // 32 for p in pubs if p is not None}
+    if len(n_public) > 1:
+        raise StarkError(3, "verify_circuit_batch", "public wire counts differ")
+    texts = [None if p is None else _json_bytes(p) for p in proofs]
+    pub_ptrs = (ctypes.c_char_p * n)(*pubs)
+    js_ptrs = (ctypes.c_char_p * n)(*texts)
+    lens = (ctypes.c_size_t * n)(*[0 if t is None else len(t) for t in texts])
+    sts = (ctypes.c_int * n)()
+    why = (ctypes.c_uint32 * n)()
+    rc = ctx.lib.stark_verify_r1cs_circuit_batch(ctx.h, circuit.h, pub_ptrs, n_public.pop() if n_public else 0, js_ptrs,
+                                                 lens, n, sts, why)
+    ctx.check(rc, "verify_circuit_batch")
+    return [(int(sts[b]), int(why[b])) for b in range(n)]
+
+
 def verify_with_wtns(ctx: Context, r1cs: bytes, wtns: bytes, proof) -> bool:
     """verify_with_file_path (run.rs:556-592) on file contents."""
     js = _json_bytes(proof)
