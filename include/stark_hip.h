@@ -42,8 +42,10 @@ extern "C" {
  * 6: stark_eval_poly_multipoint(_dev), stark_ctx_set_multipoint_tree_min, stark_divrem_polys.
  * 7: stark_merkle_forest_*, stark_prove_low_degree_batch(_dev).
  * 8: stark_prove_r1cs_circuit_batch, stark_ctx_set_prove_batch_limit.
- * 9: stark_verify_r1cs_circuit_batch, stark_ctx_set_verify_batch_limit, STARK_VERIFY_FAIL_*. */
-#define STARK_ABI_VERSION 9u
+ * 9: stark_verify_r1cs_circuit_batch, stark_ctx_set_verify_batch_limit, STARK_VERIFY_FAIL_*.
+ * 10: stark_verify_r1cs_circuit_batch_proofs, stark_r1cs_proof_from_parts,
+ *     stark_ctx_set_verify_batch_transcript. */
+#define STARK_ABI_VERSION 10u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -122,6 +124,13 @@ stark_status stark_ctx_set_prove_batch_limit(stark_ctx* ctx, size_t bytes);
  * chunks of one.  The buffers are reused across calls and counted in stark_ctx_memory's resident_bytes; a cap
  * below what they hold frees them at once. */
 stark_status stark_ctx_set_verify_batch_limit(stark_ctx* ctx, size_t bytes);
+/* Who derives a batched verification's transcript -- the 80 positions, each FRI layer's 40 rows, r, k and the
+ * records that tell the check kernels where a proof's openings are (no reference counterpart): 1 the host, one
+ * proof per worker; 2 the device, one workgroup per proof from the roots in the proof's block, so that the host
+ * uploads openings only; 0 the library's default (the host).  It applies to
+ * stark_verify_r1cs_circuit_batch and stark_verify_r1cs_circuit_batch_proofs and changes no status and no
+ * reason.  Any other mode is STARK_ERR_BAD_ARG. */
+stark_status stark_ctx_set_verify_batch_transcript(stark_ctx* ctx, uint32_t mode);
 
 /* ---- NTT (packages/fri/src/fft.rs) --------------------------------------- */
 /* best_fft<T>(coefficients: Vec<T>, root_of_unity: &T, log_order_of_root: u32) -> Vec<T>
@@ -557,6 +566,18 @@ stark_status stark_r1cs_proof_json_from_parts(const uint8_t m_root[32], const ui
                                               const stark_fri_layer_parts* layers, size_t n_layers,
                                               const uint8_t* last_values, size_t n_last, char* buf, size_t cap,
                                               size_t* len);
+/* A StarkProof handle over copies of the same parts (host only, no context): what a caller that holds a
+ * StarkProof value -- received over the wire, or read from another handle's accessors -- passes to
+ * stark_verify_r1cs_circuit_batch_proofs without rendering text.  The handle works with every stark_r1cs_proof_*
+ * accessor and is freed with stark_r1cs_proof_free; stark_r1cs_proof_json(_view) render its text on the first
+ * request, once.  STARK_ERR_BAD_ARG (*out NULL): a null root, set of openings, `out`, or array whose count is
+ * not zero, a leaf_len of 0, a size product that overflows.  Nothing else about the parts is judged here: the
+ * verifier judges them. */
+stark_status stark_r1cs_proof_from_parts(const uint8_t m_root[32], const uint8_t l_root[32], const uint8_t a_root[32],
+                                         const stark_branches* main_branches,
+                                         const stark_branches* linear_comb_branches,
+                                         const stark_fri_layer_parts* layers, size_t n_layers,
+                                         const uint8_t* last_values, size_t n_last, stark_r1cs_proof** out);
 /* mk_r1cs_proof (prove.rs:14-264) for rank `rank` of `world`: the trace set-up,
  * accumulator tree and transcript r on every rank, then this rank's residue
  * class of the precision domain: coset LDEs (no exchange: degree < steps <=
@@ -721,6 +742,18 @@ stark_status stark_verify_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_ci
                                              const uint8_t* const* public_wires, size_t n_public,
                                              const char* const* proof_json, const size_t* json_lens,
                                              uint32_t batch, stark_status* statuses, uint32_t* reasons);
+/* stark_verify_r1cs_circuit_batch for proofs held as handles (stark_prove_r1cs_circuit(_batch)'s, or
+ * stark_r1cs_proof_from_parts'): no text is rendered or parsed, the openings are read in place.  The contract is
+ * that call's with proofs[b] where it takes proof_json[b] and json_lens[b]: the same whole-call errors (a null
+ * `proofs` among them), batch == 0, batch > 65535, statuses == NULL, reasons, isolation and chunking; a null
+ * proofs[b] is that entry's STARK_ERR_BAD_ARG.  statuses[b] and reasons[b] are what
+ * stark_verify_r1cs_circuit_batch returns for stark_r1cs_proof_json of the same handle.  A handle is untrusted
+ * input: every index is derived from its roots, the prover's own index vectors are never read, and a handle of
+ * another structure than the circuit implies goes through the single-proof verifier. */
+stark_status stark_verify_r1cs_circuit_batch_proofs(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
+                                                    const uint8_t* const* public_wires, size_t n_public,
+                                                    const stark_r1cs_proof* const* proofs, uint32_t batch,
+                                                    stark_status* statuses, uint32_t* reasons);
 /* The same from the .r1cs bytes (read_r1cs + verify_with_witness). */
 stark_status stark_verify_r1cs_bytes(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len,
                                      const uint8_t* public_wires, size_t n_public, const char* proof_json,

@@ -403,6 +403,12 @@ stark_status stark_ctx_set_verify_batch_limit(stark_ctx* ctx, size_t bytes) {
   return STARK_OK;
 }
 
+stark_status stark_ctx_set_verify_batch_transcript(stark_ctx* ctx, uint32_t mode) {
+  if (!ctx || mode > 2) return STARK_ERR_BAD_ARG;
+  ctx->verify_batch_transcript = mode;
+  return STARK_OK;
+}
+
 stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t* cache_limit,
                               size_t* resident_bytes) {
   if (!ctx) return STARK_ERR_BAD_ARG;

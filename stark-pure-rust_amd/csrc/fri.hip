@@ -848,9 +848,9 @@ void fri_proof_json_pieces(const stark_fri_proof* proof, JsonPieces& j) {
       j.text("{\"Middle\":{\"root2\":");
       j.bytes(L.root2, 32);
       j.text(",\"column_branches\":");
-      j.branches(L.col_leaves, 32, L.col_nodes, L.col_idx.size(), L.col_depth);
+      j.branches(L.col_leaves, L.col_leaf_len, L.col_nodes, L.col_idx.size(), L.col_depth);
       j.text(",\"poly_branches\":");
-      j.branches(L.poly_leaves, 32, L.poly_nodes, L.poly_idx.size(), L.poly_depth);
+      j.branches(L.poly_leaves, L.poly_leaf_len, L.poly_nodes, L.poly_idx.size(), L.poly_depth);
       j.text("}}");
     }
   }
@@ -1052,6 +1052,89 @@ stark_status stark_r1cs_proof_json_from_parts(const uint8_t m_root[32], const ui
   return STARK_OK;
 }
 
+// A handle over copies of the caller's parts.  Only what the copies need is judged here: the verifier judges
+// the rest (a handle is untrusted input to it).
+stark_status stark_r1cs_proof_from_parts(const uint8_t m_root[32], const uint8_t l_root[32], const uint8_t a_root[32],
+                                         const stark_branches* main_branches,
+                                         const stark_branches* linear_comb_branches,
+                                         const stark_fri_layer_parts* layers, size_t n_layers,
+                                         const uint8_t* last_values, size_t n_last, stark_r1cs_proof** out) {
+  if (!out) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  if (!m_root || !l_root || !a_root || !main_branches || !linear_comb_branches) return STARK_ERR_BAD_ARG;
+  if ((n_layers && !layers) || (n_last && !last_values)) return STARK_ERR_BAD_ARG;
+  size_t last_bytes = 0;
+  if (__builtin_mul_overflow(n_last, (size_t)32, &last_bytes)) return STARK_ERR_BAD_ARG;
+  // k x leaf_len and k x depth x 32 bytes of one set of openings, copied.
+  auto take = [](const stark_branches& B, std::vector<uint8_t>& leaves, std::vector<uint8_t>& nodes) {
+    size_t lb = 0, nb = 0;
+    if (B.leaf_len == 0 || __builtin_mul_overflow(B.k, B.leaf_len, &lb) || __builtin_mul_overflow(B.k, B.depth, &nb) ||
+        __builtin_mul_overflow(nb, (size_t)32, &nb))
+      return false;
+    if ((lb && !B.leaves) || (nb && !B.nodes)) return false;
+    leaves.assign(B.leaves, B.leaves + lb);
+    nodes.assign(B.nodes, B.nodes + nb);
+    return true;
+  };
+  std::unique_ptr<stark_r1cs_proof> p(new stark_r1cs_proof);
+  memcpy(p->m_root, m_root, 32);
+  memcpy(p->l_root, l_root, 32);
+  memcpy(p->a_root, a_root, 32);
+  p->json_lazy = true;
+  if (!take(*main_branches, p->m_leaves, p->m_nodes) || !take(*linear_comb_branches, p->l_leaves, p->l_nodes))
+    return STARK_ERR_BAD_ARG;
+  p->m_leaf_len = main_branches->leaf_len;
+  p->l_leaf_len = linear_comb_branches->leaf_len;
+  p->depth = main_branches->depth;
+  p->l_depth = linear_comb_branches->depth;
+  std::unique_ptr<stark_fri_proof> fri(new stark_fri_proof);
+  for (size_t l = 0; l < n_layers; ++l) {
+    const stark_fri_layer_parts& P = layers[l];
+    if (!P.root2) return STARK_ERR_BAD_ARG;
+    stark_fri_layer L;
+    memcpy(L.root2, P.root2, 32);
+    if (!take(P.column, L.col_leaves, L.col_nodes) || !take(P.poly, L.poly_leaves, L.poly_nodes))
+      return STARK_ERR_BAD_ARG;
+    L.col_idx.resize(P.column.k);  // (counts only: the prover's indices are unknown here and nothing reads them)
+    L.poly_idx.resize(P.poly.k);
+    L.col_leaf_len = P.column.leaf_len;
+    L.poly_leaf_len = P.poly.leaf_len;
+    L.col_depth = P.column.depth;
+    L.poly_depth = P.poly.depth;
+    fri->layers.push_back(std::move(L));
+  }
+  stark_fri_layer last;
+  last.last = true;
+  memset(last.root2, 0, 32);
+  if (last_bytes) last.last_values.assign(last_values, last_values + last_bytes);
+  fri->layers.push_back(std::move(last));
+  p->fri = fri.release();
+  *out = p.release();
+  return STARK_OK;
+}
+
+}  // extern "C"
+
+namespace stark {
+const JsonText& r1cs_proof_text(const stark_r1cs_proof* proof) {
+  if (proof->json_lazy)
+    std::call_once(proof->json_once, [proof] {
+      JsonPieces j;
+      stark_proof_json_head(proof->m_root, proof->l_root, proof->a_root,
+                            {proof->m_leaves, proof->m_leaf_len, proof->m_nodes,
+                             proof->m_leaves.size() / proof->m_leaf_len, proof->depth_of(0)},
+                            {proof->l_leaves, proof->l_leaf_len, proof->l_nodes,
+                             proof->l_leaves.size() / proof->l_leaf_len, proof->depth_of(1)},
+                            j);
+      fri_proof_json_pieces(proof->fri, j);
+      j.text("}");
+      j.render(proof->json);
+    });
+  return proof->json;
+}
+}  // namespace stark
+
+extern "C" {
 
 stark_status stark_fri_proof_json(const stark_fri_proof* proof, char* buf, size_t cap, size_t* len) {
   if (!proof || !len) return STARK_ERR_BAD_ARG;

@@ -11,6 +11,7 @@
 #include <future>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -156,6 +157,9 @@ constexpr size_t kDefaultProveBatchLimit = (size_t)6 << 30;
 // as consecutive chunks.  A proof stages its leaves, a 32-B node per tree level of each path and 32 B per record
 // (DESIGN.md 5.6.1): 0.9 MB at precision 2^18, some 280 proofs per chunk.
 constexpr size_t kDefaultVerifyBatchLimit = (size_t)256 << 20;
+// Who derives the batched verifier's transcript by default: 1 the host, 2 the device
+// (stark_ctx_set_verify_batch_transcript).
+constexpr uint32_t kDefaultVerifyTranscript = 1;
 
 }  // namespace stark
 
@@ -196,6 +200,9 @@ struct stark_ctx {
   // stark::kDefaultVerifyBatchLimit); reused across calls, freed when the cap is lowered below what they hold.
   stark::DevBuf verify_batch;
   size_t verify_batch_limit = 0;
+  // Who derives a chain proof's indices, challenges and records (stark_ctx_set_verify_batch_transcript): 0 the
+  // default (stark::kDefaultVerifyTranscript), 1 the host, 2 the device.
+  uint32_t verify_batch_transcript = 0;
   // pinned host scratch (ctx_pinned)
   void* pinned[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t pinned_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -488,7 +495,7 @@ void stark_proof_json_head(const uint8_t m_root[32], const uint8_t l_root[32], c
 
 // The four main-tree rows a spot check at position j opens (prove.rs:337-362, verify.rs:86-118): j, one
 // step back, and the rows one and two thirds of the original steps ahead.
-inline void spot_rows(size_t j, size_t os, size_t skips, size_t prec, size_t out[4]) {
+__host__ __device__ inline void spot_rows(size_t j, size_t os, size_t skips, size_t prec, size_t out[4]) {
   out[0] = j;
   out[1] = (j + prec - skips) % prec;
   out[2] = (j + os / 3 * skips) % prec;
@@ -502,7 +509,8 @@ struct stark_fri_layer {
   bool last = false;
   uint8_t root2[32];
   size_t col_depth = 0, poly_depth = 0;
-  std::vector<size_t> col_idx, poly_idx;
+  std::vector<size_t> col_idx, poly_idx;  // the prover's own indices (a verifier never reads them)
+  size_t col_leaf_len = 32, poly_leaf_len = 32;  // (other than 32 only in a handle made from a caller's parts)
   std::vector<uint8_t> col_leaves, col_nodes;    // 32 B leaves, depth*32 B paths
   std::vector<uint8_t> poly_leaves, poly_nodes;
   std::vector<uint8_t> last_values;              // n * 32 B
@@ -514,14 +522,27 @@ struct stark_fri_proof {
 
 struct stark_r1cs_proof {
   uint8_t m_root[32], l_root[32], a_root[32];
-  stark::JsonText json;
+  // The serde_json text: rendered by the prover, or (json_lazy, a handle of stark_r1cs_proof_from_parts) on the
+  // first request, once (stark::r1cs_proof_text).
+  mutable stark::JsonText json;
+  mutable std::once_flag json_once;
+  bool json_lazy = false;
   // The parts, for callers that build their own StarkProof value (stark_r1cs_proof_branches / _fri):
   // main and linear-combination openings (leaves, then depth siblings per opening, leaf to root).
   size_t depth = 0;
+  // (A prover's handle has 256-B main leaves, 32-B L leaves and one depth; one made from a caller's parts holds
+  // whatever it was given, l_depth included.)
+  size_t m_leaf_len = 256, l_leaf_len = 32, l_depth = SIZE_MAX;
+  size_t depth_of(int which) const { return which == 0 || l_depth == SIZE_MAX ? depth : l_depth; }
   std::vector<uint8_t> m_leaves, m_nodes, l_leaves, l_nodes;
   stark_fri_proof* fri = nullptr;
   ~stark_r1cs_proof() { stark_fri_proof_free(fri); }
 };
+
+namespace stark {
+// The proof's serde_json text, rendered first where the handle holds parts only (fri.hip).
+const JsonText& r1cs_proof_text(const stark_r1cs_proof* proof);
+}  // namespace stark
 
 namespace stark {
 

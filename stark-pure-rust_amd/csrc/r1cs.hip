@@ -28,6 +28,7 @@
 #include "internal.h"
 #include "blake2s.h"
 #include "fe_db.h"
+#include "transcript_dev.h"
 
 namespace stark {
 void json_bytes(std::string& o, const uint8_t* p, size_t n);
@@ -94,19 +95,7 @@ struct Transcript {
   uint32_t c_db[33][72];  // R^-1 | a_0..a_7 | inv(Z) R^k at t = i mod 8, table 9 + 8 k + t (invz_m)
 };
 
-__device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
-
-// Digest of a 32- or 33-byte message (words LE, zero padded).
-__device__ __forceinline__ void b2s_short(const uint32_t* w, uint32_t extra_byte, uint32_t len, uint32_t out[8]) {
-  uint32_t m[16];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) m[i] = w[i];
-  m[8] = extra_byte;
-#pragma unroll
-  for (int i = 9; i < 16; ++i) m[i] = 0;
-  b2s_init(out);
-  b2s_compress(out, m, len, 0, true);
-}
+// (bswap32, b2s_short, challenge_r and challenge_k: transcript_dev.h, shared with the batched verifier.)
 
 // The digit-basis table of a canonical constant c: limb j of c 2^(32 i) mod p at 9 i + j, each row one
 // product by the Montgomery image of 2^(32 i) (Pow32), one row per thread.
@@ -156,15 +145,7 @@ __global__ void r1cs_r_kernel(const uint32_t* __restrict__ a_root, uint32_t prec
     b2s_short(data + 8, 0, 32, data + 16);
     fe r[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const uint32_t v = bswap32(data[8 * c + i]) & prec_mask;  // BE word mod 2^k
-        r[c].w[i] = bswap32(v);                                  // BE bytes read as LE words
-      }
-#pragma unroll
-      for (int k = 0; k < 5; ++k) fe_reduce_once(r[c]);
-    }
+    for (int c = 0; c < 3; ++c) r[c] = challenge_r(data + 8 * c, prec_mask);
     tr->r0 = r[0];
     tr->r1_m = fe_mul(r[1], r2);
     tr->r2_m = fe_mul(r[2], r2);
@@ -203,12 +184,7 @@ __device__ __forceinline__ void r1cs_k_body(const uint32_t* __restrict__ m_root,
   } else if (i <= 10) {
     uint32_t h[8];
     b2s_short(m_root, i, 33, h);
-    fe k;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) k.w[j] = bswap32(h[7 - j]);
-#pragma unroll
-    for (int t = 0; t < 5; ++t) fe_reduce_once(k);
-    ks[i] = fe_mul(k, r2);
+    ks[i] = fe_mul(challenge_k(h), r2);
     tr->k_m[i] = ks[i];
   }
   __syncthreads();
@@ -2609,10 +2585,11 @@ stark_status stark_mk_r1cs_proof(stark_ctx* ctx, const uint64_t* witness_trace, 
 
 stark_status stark_r1cs_proof_json(const stark_r1cs_proof* proof, char* buf, size_t cap, size_t* len) {
   if (!proof || !len) return STARK_ERR_BAD_ARG;
-  *len = proof->json.size();
+  const JsonText& text = r1cs_proof_text(proof);
+  *len = text.size();
   if (buf && cap) {
-    const size_t k = proof->json.size() < cap ? proof->json.size() : cap;
-    host_memcpy(buf, proof->json.data(), k);
+    const size_t k = text.size() < cap ? text.size() : cap;
+    host_memcpy(buf, text.data(), k);
     if (k < cap) buf[k] = 0;
   }
   return STARK_OK;
@@ -2620,8 +2597,9 @@ stark_status stark_r1cs_proof_json(const stark_r1cs_proof* proof, char* buf, siz
 
 stark_status stark_r1cs_proof_json_view(const stark_r1cs_proof* proof, const char** data, size_t* len) {
   if (!proof || !data || !len) return STARK_ERR_BAD_ARG;
-  *data = proof->json.data();
-  *len = proof->json.size();
+  const JsonText& text = r1cs_proof_text(proof);
+  *data = text.data();
+  *len = text.size();
   return STARK_OK;
 }
 
@@ -2638,12 +2616,12 @@ stark_status stark_r1cs_proof_branches(const stark_r1cs_proof* proof, int which,
                                        size_t* depth, uint8_t* leaves, size_t leaves_cap, uint8_t* nodes,
                                        size_t nodes_cap) {
   if (!proof || (which != 0 && which != 1)) return STARK_ERR_BAD_ARG;
-  const size_t ll = which == 0 ? 256 : 32;
+  const size_t ll = which == 0 ? proof->m_leaf_len : proof->l_leaf_len;
   const std::vector<uint8_t>& lv = which == 0 ? proof->m_leaves : proof->l_leaves;
   const std::vector<uint8_t>& nd = which == 0 ? proof->m_nodes : proof->l_nodes;
   if (k) *k = lv.size() / ll;
   if (leaf_len) *leaf_len = ll;
-  if (depth) *depth = proof->depth;
+  if (depth) *depth = proof->depth_of(which);
   // capacities checked before either buffer is written
   if ((leaves && leaves_cap < lv.size()) || (nodes && nodes_cap < nd.size())) return STARK_ERR_BAD_LENGTH;
   if (leaves) memcpy(leaves, lv.data(), lv.size());

@@ -13,6 +13,12 @@
 // other proof goes through the single-proof verifier, so each status is stark_verify_r1cs_circuit's.  Nothing
 // a proof's text supplies is used as a length or an offset on the device: the records hold offsets the host
 // computed from the circuit's shape, and indices the sampler produced below the trees' sizes.
+//
+// A proof comes as serde_json text or as a stark_r1cs_proof handle (views over its vectors, no text: view_proof).
+// Two more launches may precede the three: verify_transcript_batch_kernel derives a chain proof's indices,
+// challenges and records from the roots in its block, one workgroup per proof, where the context asks for the
+// device's transcript (the host then uploads openings only); verify_interp2_batch_kernel forms every chain proof's
+// I2 from the Lagrange basis of the circuit's boundary points where that matrix is small enough.
 #include <string.h>
 
 #include <algorithm>
@@ -21,6 +27,7 @@
 
 #include "internal.h"
 #include "merkle_dev.h"
+#include "transcript_dev.h"
 #include "verify_in.h"
 
 namespace stark {
@@ -29,6 +36,9 @@ namespace {
 constexpr uint32_t kSpots = 80, kMainPer = 4, kRows = 40, kPolyPer = 4;  // verify.rs:86-118, fri.rs:288-316
 constexpr uint32_t kMainLeaf = 256, kMaxLayers = 16;
 constexpr uint32_t kThreads = 64;  // one wave per workgroup: a chunk's few thousand lanes spread over the CUs
+
+// The roots come first in a block: m_root, l_root, then each Middle layer's root2 (a_root follows them, Shape).
+constexpr size_t kRootM = 0, kRootL = 32, kRoot2 = 64;
 
 // One Merkle path (Proof::validate, merkle_tree.rs:25-43): byte offsets into the chunk's image.
 struct PathRec {
@@ -245,13 +255,171 @@ __global__ __launch_bounds__(kThreads) void verify_spot_batch_kernel(const uint8
   ok[i] = good;
 }
 
+// ---- the transcript and I2 on the device ----
+
+// Where a chunk's parts are, as the transcript kernel takes them: the Shape and ChunkPlan below, in 32 bits (a
+// chunk's image stays under 4 GiB).  Everything here is a function of the circuit and of the number of chain
+// proofs in the chunk; nothing comes from a proof.
+struct TranscriptArgs {
+  uint32_t nb, layers, depth, prec, os, skips;
+  uint32_t o_paths, o_rows, o_spots, o_blocks, block;
+  uint32_t o_aroot, o_consts, o_i2, o_main_leaf, o_main_nodes, o_l_leaf, o_l_nodes;
+  uint32_t o_col_leaf[kMaxLayers], o_col_nodes[kMaxLayers], o_poly_leaf[kMaxLayers], o_poly_nodes[kMaxLayers];
+  fe r2m, one;
+};
+
+template <class T>
+__device__ __forceinline__ void store_rec(T* p, const T& r) {
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(&r);
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// get_pseudorandom_indices' map of one big-endian word (fri/src/utils.rs:101-109; fri.hip fri_indices_block): below
+// `modulus`, never a multiple of `excl`.  (plan_shape checked modulus (excl - 1) / excl > 0 for every tree.)
+__device__ __forceinline__ uint32_t sampled_index(uint32_t le_word, uint32_t modulus, uint32_t excl) {
+  const uint32_t real_mod = (uint32_t)((uint64_t)modulus * (excl - 1) / excl);
+  const uint32_t v = __builtin_bswap32(le_word) % real_mod;
+  return v + 1 + v / (excl - 1);
+}
+
+constexpr uint32_t kChainWords = 80;                // the longest chain: the 80 positions' words
+constexpr uint32_t kMaxChains = kMaxLayers + 12;    // l_root, the layers, a_root, k_1..k_10
+
+// Everything the host's pack derives from a chain proof's roots, one workgroup (one wave) per proof, from the
+// roots in the proof's block: the 80 positions (l_root), each Middle layer's 40 rows (its root2), r (a_root)
+// and k (m_root) into the block's constant slots, and every PathRec, RowRec and SpotRec of the proof in pack's
+// order.  The Blake2s chains are independent -- l_root's 9 dependent hashes, 4 per layer, 2 for r, one each for
+// k_1..k_10 -- so each runs on a lane of its own, all through the same loop (a lane past its chain's end idles);
+// then every lane derives indices and writes records.  No workgroup reads what another writes.
+__global__ __launch_bounds__(kThreads) void verify_transcript_batch_kernel(uint8_t* arena, TranscriptArgs A) {
+  __shared__ uint32_t chain[kMaxChains][kChainWords];  // a chain's seed, then its digests, as LE words
+  __shared__ uint32_t pos[kSpots];
+  __shared__ uint32_t ys[kMaxLayers][kRows];
+  const uint32_t t = threadIdx.x, k = blockIdx.x;
+  const uint32_t blk = A.o_blocks + k * A.block;
+  const uint32_t n_chains = A.layers + 12;
+  {
+    // Lane t's chain: its seed's place in the block, its count of dependent hashes, and the byte that follows
+    // the seed in its first message (k_i hashes m_root || i, 33 bytes).
+    uint32_t seed = blk + kRootL, hashes = 9, extra = 0;
+    if (t >= 1 && t <= A.layers) {
+      seed = blk + kRoot2 + 32 * (t - 1);
+      hashes = 4;
+    } else if (t == A.layers + 1) {
+      seed = blk + A.o_aroot;
+      hashes = 2;
+    } else if (t > A.layers + 1) {
+      seed = blk + kRootM;
+      hashes = 1;
+      extra = t - A.layers - 1;
+    }
+    if (t >= n_chains) hashes = 0;
+    uint32_t w[8];
+    if (t < n_chains) {
+      const Digest d = load_digest(reinterpret_cast<const Digest*>(arena + seed));
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        w[i] = d.h[i];
+        chain[t][i] = w[i];
+      }
+    }
+#pragma unroll 1
+    for (uint32_t b = 0; b < 9; ++b) {
+      if (b < hashes) {
+        uint32_t h[8];
+        b2s_short(w, extra, extra ? 33 : 32, h);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          w[i] = h[i];
+          chain[t][8 * (b + 1) + i] = h[i];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // Indices and challenges.
+  for (uint32_t i = t; i < kSpots; i += kThreads) pos[i] = sampled_index(chain[0][i], A.prec, A.skips);
+  for (uint32_t i = t; i < A.layers * kRows; i += kThreads) {
+    const uint32_t l = i / kRows, y = i % kRows;
+    ys[l][y] = sampled_index(chain[1 + l][y], A.prec >> (2 * l + 2), A.skips);
+  }
+  fe* const consts = reinterpret_cast<fe*>(arena + blk + A.o_consts);
+  if (t < 3) {
+    fe_store(consts + t, fe_mul(challenge_r(&chain[A.layers + 1][8 * t], A.prec - 1), A.r2m));
+  } else if (t == 3) {
+    fe_store(consts + 3, A.one);  // k_0 = 1
+  } else if (t < 14) {
+    fe_store(consts + t, fe_mul(challenge_k(&chain[A.layers + 1 + (t - 3)][8]), A.r2m));  // k_(t-3) at slot 3 + (t-3)
+  }
+  __syncthreads();
+  // The records, in pack's order: paths class-major (main, L, then each layer's polynomial and column openings),
+  // rows layer-major, spots.
+  PathRec* const paths = reinterpret_cast<PathRec*>(arena + A.o_paths);
+  RowRec* const rows = reinterpret_cast<RowRec*>(arena + A.o_rows);
+  SpotRec* const spots = reinterpret_cast<SpotRec*>(arena + A.o_spots);
+  uint32_t cls = 0;
+  for (uint32_t q = t; q < kSpots * kMainPer; q += kThreads) {
+    size_t rows4[4];
+    spot_rows(pos[q / kMainPer], A.os, A.skips, A.prec, rows4);
+    store_rec(paths + cls + k * kSpots * kMainPer + q,
+              PathRec{blk + (uint32_t)kRootM, blk + A.o_main_leaf + kMainLeaf * q, blk + A.o_main_nodes + 32 * A.depth * q,
+                      (uint32_t)rows4[q % kMainPer], kMainLeaf, A.depth, 0, 0});
+  }
+  cls += A.nb * kSpots * kMainPer;
+  for (uint32_t i = t; i < kSpots; i += kThreads) {
+    store_rec(paths + cls + k * kSpots + i, PathRec{blk + (uint32_t)kRootL, blk + A.o_l_leaf + 32 * i,
+                                                     blk + A.o_l_nodes + 32 * A.depth * i, pos[i], 32, A.depth, 0, 0});
+    store_rec(spots + k * kSpots + i, SpotRec{blk + A.o_main_leaf + kMainLeaf * kMainPer * i, blk + A.o_l_leaf + 32 * i,
+                                               blk + A.o_consts, blk + A.o_i2, pos[i], 0, 0, 0});
+  }
+  cls += A.nb * kSpots;
+  for (uint32_t l = 0; l < A.layers; ++l) {
+    const uint32_t root_l = blk + (uint32_t)(l == 0 ? kRootL : kRoot2 + 32 * (l - 1)), root2 = blk + (uint32_t)kRoot2 + 32 * l;
+    const uint32_t pd = A.depth - 2 * l, cd = A.depth - 2 * l - 2, quarter = A.prec >> (2 * l + 2);
+    for (uint32_t q = t; q < kRows * kPolyPer; q += kThreads)
+      store_rec(paths + cls + k * kRows * kPolyPer + q,
+                PathRec{root_l, blk + A.o_poly_leaf[l] + 32 * q, blk + A.o_poly_nodes[l] + 32 * pd * q,
+                        (q % kPolyPer) * quarter + ys[l][q / kPolyPer], 32, pd, 0, 0});
+    cls += A.nb * kRows * kPolyPer;
+    for (uint32_t i = t; i < kRows; i += kThreads) {
+      store_rec(paths + cls + k * kRows + i, PathRec{root2, blk + A.o_col_leaf[l] + 32 * i,
+                                                      blk + A.o_col_nodes[l] + 32 * cd * i, ys[l][i], 32, cd, 0, 0});
+      store_rec(rows + (l * A.nb + k) * kRows + i, RowRec{root_l, blk + A.o_col_leaf[l] + 32 * i,
+                                                           blk + A.o_poly_leaf[l] + 32 * kPolyPer * i, ys[l][i], l, 0, 0, 0});
+    }
+    cls += A.nb * kRows;
+  }
+}
+
+// I2 of every chain proof at once.  The boundary points are the circuit's, so I2_b = sum_k pub_b[wire_k] L_k
+// with L_k the k-th Lagrange basis polynomial over them: one lane per (proof, coefficient j) forms the n_b-term
+// sum over column j of the basis matrix and writes the block's I2 slot j as a Montgomery image.  mat[k n_b + j]
+// holds coefficient j of L_k times R^2, so its product with the wire's 32 bytes as they are (any value below
+// 2^256, as from_bytes_le takes them) is the term's Montgomery image; wire[k] < n_public (checked by the host).
+__global__ __launch_bounds__(kThreads) void verify_interp2_batch_kernel(uint8_t* arena, const fe* __restrict__ mat,
+                                                                         const uint32_t* __restrict__ wire, uint32_t n_b,
+                                                                         uint32_t o_blocks, uint32_t block,
+                                                                         uint32_t o_pub, uint32_t o_i2) {
+  const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
+  if (j >= n_b) return;
+  const uint32_t blk = o_blocks + blockIdx.y * block;
+  fe acc = fe_zero();
+  for (uint32_t k = 0; k < n_b; ++k)
+    acc = fe_add(acc, fe_mul(arena_fe(arena, blk + o_pub + 32 * wire[k]), fe_load(mat + (size_t)k * n_b + j)));
+  fe_store(reinterpret_cast<fe*>(arena + blk + o_i2) + j, acc);
+}
+
 // ---- host ----
 
 // What the circuit implies of a proof's structure, and where a proof's parts are in its block of the image.
 struct Shape {
   uint32_t depth = 0, layers = 0;  // log2 precision; FriProof::Middle layers
   size_t n_b = 0;                  // boundary points
+  size_t n_public = 0;             // public wires
   // offsets in a proof's block (bytes; everything is a multiple of 32)
+  size_t o_aroot = 0, o_pub = 0;   // a_root and the public wires as given (what the device forms derive from)
   size_t o_consts = 0, o_i2 = 0, o_main_leaf = 0, o_main_nodes = 0, o_l_leaf = 0, o_l_nodes = 0;
   size_t o_col_leaf[kMaxLayers], o_col_nodes[kMaxLayers], o_poly_leaf[kMaxLayers], o_poly_nodes[kMaxLayers];
   size_t block = 0;  // bytes per proof
@@ -263,12 +431,12 @@ struct Shape {
   size_t staged() const { return block + 32 * checks(); }  // a proof's block and records
 };
 
-// The roots come first in a block: m_root, l_root, then each Middle layer's root2.
-constexpr size_t kRootM = 0, kRootL = 32, kRoot2 = 64;
-
 // False where the chain cannot take the circuit at all (every proof then goes to the single-proof verifier).
 bool plan_shape(const PreparedCircuit& c, const VerifyDomain& d, Shape& s) {
-  if (c.spot || !c.col[0] || d.prec > ((uint64_t)1 << 28)) return false;
+  // (The sampler's bounds on the precision, utils.rs:88 and :101, for the 80 positions and for r: they depend on
+  // the circuit alone, so a precision the sampler refuses sends every proof to the single-proof verifier.)
+  if (c.spot || !c.col[0] || d.prec >= ((uint64_t)1 << 24) || d.skips < 2 || d.prec * (d.skips - 1) / d.skips == 0)
+    return false;
   while (((uint64_t)1 << s.depth) < d.prec) ++s.depth;
   // The layers prove_low_degree makes of precision values below degree precision / 4 (fri.rs:64-66; fri.hip
   // fri_check), each with the sampler's bounds on its column (utils.rs:88).
@@ -281,12 +449,15 @@ bool plan_shape(const PreparedCircuit& c, const VerifyDomain& d, Shape& s) {
   }
   if (s.layers + 1 > kMaxLayers) return false;
   s.n_b = c.pfi.size() / 2;
+  s.n_public = c.n_public;
   size_t at = 32 * (2 + (size_t)s.layers);
   auto take = [&](size_t bytes) {
     const size_t o = at;
     at += bytes;
     return o;
   };
+  s.o_aroot = take(32);
+  s.o_pub = take(32 * s.n_public);
   s.o_consts = take(32 * 14);
   s.o_i2 = take(32 * s.n_b);
   s.o_main_leaf = take((size_t)kSpots * kMainPer * kMainLeaf);
@@ -327,9 +498,61 @@ bool in_shape(const ProofIn& pr, const Shape& s) {
   return branches_are(pr.main, kSpots * kMainPer, kMainLeaf, s.depth) && branches_are(pr.lcomb, kSpots, 32, s.depth);
 }
 
+// A handle's parts as the parsed proof the verifier reads: views over the handle's vectors (nothing is copied
+// but the Last layer's values, nothing allocated per opening).  A handle is untrusted input -- anything can be
+// made into one (stark_r1cs_proof_from_parts) -- so only sizes the vectors really have become views, the
+// prover's own index vectors are never read, and the views pass the same screen as a parsed text.
+bool view_branches(const std::vector<uint8_t>& leaves, size_t leaf_len, const std::vector<uint8_t>& nodes, size_t depth,
+                   std::vector<Branch>& out) {
+  if (leaf_len == 0 || leaves.size() % leaf_len) return false;
+  const size_t k = leaves.size() / leaf_len;
+  if (k == 0) return nodes.empty();
+  if (nodes.size() % (32 * k) || nodes.size() / (32 * k) != depth) return false;
+  out.resize(k);
+  for (size_t i = 0; i < k; ++i) {
+    out[i].leaf = Bytes{leaves.data() + i * leaf_len, leaf_len};
+    out[i].nodes = Bytes{nodes.data() + i * depth * 32, depth * 32};
+  }
+  return true;
+}
+bool view_proof(const stark_r1cs_proof& h, ProofIn& pr) {
+  if (!h.fri) return false;
+  memcpy(pr.m_root, h.m_root, 32);
+  memcpy(pr.l_root, h.l_root, 32);
+  memcpy(pr.a_root, h.a_root, 32);
+  if (!view_branches(h.m_leaves, h.m_leaf_len, h.m_nodes, h.depth_of(0), pr.main) ||
+      !view_branches(h.l_leaves, h.l_leaf_len, h.l_nodes, h.depth_of(1), pr.lcomb))
+    return false;
+  pr.fri.resize(h.fri->layers.size());
+  for (size_t l = 0; l < pr.fri.size(); ++l) {
+    const stark_fri_layer& L = h.fri->layers[l];
+    FriIn& f = pr.fri[l];
+    f.last = L.last;
+    if (L.last) {
+      for (size_t i = 0; i + 32 <= L.last_values.size(); i += 32)
+        f.last_vals.emplace_back(L.last_values.data() + i, L.last_values.data() + i + 32);
+      continue;
+    }
+    memcpy(f.root2, L.root2, 32);
+    if (!view_branches(L.col_leaves, L.col_leaf_len, L.col_nodes, L.col_depth, f.col) ||
+        !view_branches(L.poly_leaves, L.poly_leaf_len, L.poly_nodes, L.poly_depth, f.poly))
+      return false;
+  }
+  return true;
+}
+
+// One entry's proof as the caller gave it: serde_json text, or a handle.
+struct ProofSrc {
+  const char* json = nullptr;
+  size_t json_len = 0;
+  const stark_r1cs_proof* handle = nullptr;
+  bool is_handle = false;
+};
+
 // One entry of the batch on its way through a chunk.
 struct Item {
   ProofIn pr;
+  const uint8_t* pub_bytes = nullptr;
   std::vector<HostFp> pub;
   bool chain = false;      // enters the device chain
   bool fallback = false;   // goes to verify_r1cs
@@ -343,14 +566,18 @@ struct Item {
 };
 
 // Everything of entry b that needs neither the device nor the worker pool: the parse, the reference's first
-// checks, the shape screen and the indices.
-void screen(const PreparedCircuit& c, const VerifyDomain& d, const Shape& s, bool chain_ok, const uint8_t* pub_bytes,
-            size_t n_public, const char* json, size_t json_len, bool serial_parse, Item& it) {
+// checks, the shape screen and, with the host's transcript, the indices and challenges (with the device's, the
+// transcript kernel derives them from the roots in the proof's block and the host calls no sampler).
+void screen(const PreparedCircuit& c, const VerifyDomain& d, const Shape& s, bool chain_ok, bool device_tr,
+            const uint8_t* pub_bytes, size_t n_public, const ProofSrc& src, bool serial_parse, Item& it) {
   const FieldHost& F = FieldHost::get();
-  if (!pub_bytes || !json || !read_proof(json, json_len, it.pr, serial_parse)) {
+  const bool read = src.is_handle ? src.handle && view_proof(*src.handle, it.pr)
+                                  : src.json && read_proof(src.json, src.json_len, it.pr, serial_parse);
+  if (!pub_bytes || !read) {
     it.st = STARK_ERR_BAD_ARG;  // (stark_verify_r1cs_circuit's null checks; serde_json::from_reader fails, run.rs:579)
     return;
   }
+  it.pub_bytes = pub_bytes;
   if (n_public != c.n_public) {
     it.st = STARK_ERR_BAD_ARG;
     return;
@@ -364,12 +591,14 @@ void screen(const PreparedCircuit& c, const VerifyDomain& d, const Shape& s, boo
   }
   it.fallback = true;
   if (!chain_ok || !in_shape(it.pr, s)) return;
-  if (!sampler(it.pr.l_root, d.prec, kSpots, (uint32_t)d.skips, it.positions)) return;
-  it.ys.resize(s.layers);
-  uint64_t deg = d.prec;
-  for (uint32_t l = 0; l < s.layers; ++l, deg /= 4)
-    if (!sampler(it.pr.fri[l].root2, deg / 4, kRows, (uint32_t)d.skips, it.ys[l])) return;
-  if (!verify_challenges(it.pr, d.prec, it.r, it.kk)) return;
+  if (!device_tr) {
+    if (!sampler(it.pr.l_root, d.prec, kSpots, (uint32_t)d.skips, it.positions)) return;
+    it.ys.resize(s.layers);
+    uint64_t deg = d.prec;
+    for (uint32_t l = 0; l < s.layers; ++l, deg /= 4)
+      if (!sampler(it.pr.fri[l].root2, deg / 4, kRows, (uint32_t)d.skips, it.ys[l])) return;
+    if (!verify_challenges(it.pr, d.prec, it.r, it.kk)) return;
+  }
   it.fallback = false;
   it.chain = true;
 }
@@ -405,16 +634,22 @@ void put_branches(uint8_t* leaves, uint8_t* nodes, const std::vector<Branch>& v)
 
 // Chain proof k of nb: its block and its records.  The path records are class-major -- main, L, then each
 // layer's polynomial and column openings -- so that equal shapes are side by side; rows are layer-major.
+// host_tr: the host writes the constants and the records (else verify_transcript_batch_kernel does, and nothing
+// of them is written or uploaded); host_i2: the host writes I2's coefficients (else verify_interp2_batch_kernel).
 void pack(const Shape& s, const VerifyDomain& d, size_t os, const ChunkPlan& p, size_t nb, size_t k, const Item& it,
-          uint8_t* img) {
+          bool host_tr, bool host_i2, uint8_t* img) {
   const size_t blk = p.o_blocks + k * s.block;
   uint8_t* const b = img + blk;
   memcpy(b + kRootM, it.pr.m_root, 32);
   memcpy(b + kRootL, it.pr.l_root, 32);
   for (uint32_t l = 0; l < s.layers; ++l) memcpy(b + kRoot2 + 32 * l, it.pr.fri[l].root2, 32);
-  for (int j = 0; j < 3; ++j) memcpy(b + s.o_consts + 32 * j, it.r[j].v, 32);
-  for (int j = 0; j < 11; ++j) memcpy(b + s.o_consts + 32 * (3 + j), it.kk[j].v, 32);
-  for (size_t j = 0; j < s.n_b; ++j) {
+  memcpy(b + s.o_aroot, it.pr.a_root, 32);
+  memcpy(b + s.o_pub, it.pub_bytes, 32 * s.n_public);
+  if (host_tr) {
+    for (int j = 0; j < 3; ++j) memcpy(b + s.o_consts + 32 * j, it.r[j].v, 32);
+    for (int j = 0; j < 11; ++j) memcpy(b + s.o_consts + 32 * (3 + j), it.kk[j].v, 32);
+  }
+  for (size_t j = 0; host_i2 && j < s.n_b; ++j) {
     if (j < it.interp2.size()) memcpy(b + s.o_i2 + 32 * j, it.interp2[j].v, 32);
     else memset(b + s.o_i2 + 32 * j, 0, 32);
   }
@@ -424,6 +659,7 @@ void pack(const Shape& s, const VerifyDomain& d, size_t os, const ChunkPlan& p, 
     put_branches(b + s.o_col_leaf[l], b + s.o_col_nodes[l], it.pr.fri[l].col);
     put_branches(b + s.o_poly_leaf[l], b + s.o_poly_nodes[l], it.pr.fri[l].poly);
   }
+  if (!host_tr) return;
   PathRec* paths = reinterpret_cast<PathRec*>(img + p.o_paths);
   auto u = [](size_t x) { return (uint32_t)x; };
   size_t cls = 0;  // the class's first record
@@ -495,24 +731,76 @@ uint32_t reasons_of(const Shape& s, const ChunkPlan& p, size_t nb, size_t k, con
   return why;
 }
 
+// The n x n Lagrange basis over the points xs (distinct), in O(n^2): Z = prod (X - x_k) once, then
+// L_k = Z / (X - x_k) / Z'(x_k) by synthetic division, Z'(x_k) being that quotient at x_k.  Row k of `out` holds
+// L_k's coefficients, low degree first, each times R^2 as verify_interp2_batch_kernel takes them.
+void lagrange_basis(const std::vector<HostFp>& xs, uint8_t* out) {
+  const FieldHost& F = FieldHost::get();
+  const size_t n = xs.size();
+  std::vector<HostFp> z(n + 1, F.zero());
+  z[0] = F.one();
+  for (size_t k = 0; k < n; ++k)  // z <- z (X - x_k)
+    for (size_t i = k + 1; i-- > 0;) {
+      z[i + 1] = F.add(z[i + 1], z[i]);
+      z[i] = F.sub(F.zero(), F.mul(z[i], xs[k]));
+    }
+  std::atomic<size_t> next{0};
+  host_parallel((unsigned)std::min<size_t>(host_threads(), (n + 15) / 16), [&](unsigned) {
+    std::vector<HostFp> q(n);
+    for (size_t k; (k = next.fetch_add(1)) < n;) {
+      q[n - 1] = z[n];
+      for (size_t i = n - 1; i > 0; --i) q[i - 1] = F.add(z[i], F.mul(xs[k], q[i]));
+      HostFp den = q[n - 1];
+      for (size_t i = n - 1; i-- > 0;) den = F.add(F.mul(den, xs[k]), q[i]);
+      const HostFp inv = F.inv(den);
+      for (size_t j = 0; j < n; ++j) {
+        const HostFp v = F.from_canonical(F.mul(q[j], inv).v);  // (the Montgomery image's limbs as a value: x R^2)
+        memcpy(out + 32 * (k * n + j), v.v, 32);
+      }
+    }
+  });
+}
+
 }  // namespace
 
-// statuses / reasons of entries [0, batch) (both non-null here).
+// statuses / reasons of entries [0, batch) (both non-null here).  The proofs are texts (proof_json, json_lens) or,
+// with `handles` non-null, handles.
 static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, const uint8_t* const* public_wires,
                                       size_t n_public, const char* const* proof_json, const size_t* json_lens,
-                                      uint32_t batch, stark_status* statuses, uint32_t* reasons) {
+                                      const stark_r1cs_proof* const* handles, uint32_t batch, stark_status* statuses,
+                                      uint32_t* reasons) {
   const FieldHost& F = FieldHost::get();
   PhaseClock clk("verify_r1cs_batch");
   const VerifyDomain d = verify_domain(c.os);
   Shape s;
   const bool chain_ok = plan_shape(c, d, s);
+  const bool device_tr =
+      (ctx->verify_batch_transcript ? ctx->verify_batch_transcript : kDefaultVerifyTranscript) == 2;
+  auto source = [&](size_t b) {
+    ProofSrc src;
+    if (handles) {
+      src.is_handle = true;
+      src.handle = handles[b];
+    } else {
+      src.json = proof_json[b];
+      src.json_len = json_lens[b];
+    }
+    return src;
+  };
   hipStream_t stream = ctx->stream;
   // The call's constants at the image's start: Zb2's roots, I3's coefficients, the layers' roots of unity and
   // sizes.  Uploaded with the first chunk that has a chain proof.
   std::vector<HostFp> bx, interp3;
-  size_t o_i3 = 0, o_lroot = 0, o_ldeg = 0, base = 0;
+  size_t o_i3 = 0, o_lroot = 0, o_ldeg = 0, o_wire = 0, o_mat = 0, base = 0;
   HostFp x_last = F.zero();
   uint32_t log_steps = 0;
+  // Chain proofs per chunk under the context's limit, and under the records' 32-bit offsets.
+  const size_t limit = std::min<size_t>(ctx->verify_batch_limit ? ctx->verify_batch_limit : kDefaultVerifyBatchLimit,
+                                        (size_t)3 << 30);
+  // I2 of a chunk's proofs by one launch over the Lagrange basis of the circuit's boundary points
+  // (verify_interp2_batch_kernel): below the threshold from which verify_interp2 interpolates on the GPU, and
+  // where the n_b x n_b matrix stays under a quarter of the cap.  Else per proof, by verify_interp2.
+  bool mat_i2 = false;
   if (chain_ok) {
     bx = verify_boundary_points(c, d);
     x_last = F.pow_u64(d.g2, (d.steps - 1) * d.skips);
@@ -521,11 +809,13 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
     o_i3 = 32 * bx.size();
     o_lroot = o_i3 + 32 * interp3.size();
     o_ldeg = o_lroot + 32 * kMaxLayers;
-    base = align256(o_ldeg + 8 * kMaxLayers);
+    o_wire = o_ldeg + 8 * kMaxLayers;
+    const size_t n_b = bx.size(), col_min = ctx->public_column_min ? ctx->public_column_min : kDefaultVerifyColumnMin;
+    mat_i2 = n_b > 0 && n_b < col_min && 32 * n_b * n_b <= limit / 4;  // (n_b < 2^21: the product fits)
+    for (size_t i = 0; mat_i2 && i < n_b; ++i) mat_i2 = c.pfi[2 * i] < c.n_public;
+    o_mat = (o_wire + (mat_i2 ? 4 * n_b : 0) + 31) & ~(size_t)31;
+    base = align256(o_mat + (mat_i2 ? 32 * n_b * n_b : 0));
   }
-  // Chain proofs per chunk under the context's limit, and under the records' 32-bit offsets.
-  const size_t limit = std::min<size_t>(ctx->verify_batch_limit ? ctx->verify_batch_limit : kDefaultVerifyBatchLimit,
-                                        (size_t)3 << 30);
   const size_t per_chunk = chain_ok ? std::max<size_t>(1, limit / s.staged()) : batch;
   bool consts_up = false;
   const size_t parse_threads = host_threads();
@@ -545,26 +835,28 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
       const char* v = getenv("STARK_VERIFY_BATCH_PARSE");
       return !v ? 0 : strcmp(v, "inner") == 0 ? 1 : strcmp(v, "worker") == 0 ? 2 : 0;
     }();
+    // (A handle has no text to read, but the host's transcript of a large chunk is still worth the workers.)
     const bool inner = forced ? forced == 1 : 2 * n < parse_threads;
     if (inner) {
       for (size_t i = 0; i < n; ++i)
-        screen(c, d, s, chain_ok, public_wires[b0 + i], n_public, proof_json[b0 + i], json_lens[b0 + i], false,
-               items[i]);
+        screen(c, d, s, chain_ok, device_tr, public_wires[b0 + i], n_public, source(b0 + i), false, items[i]);
     } else {
       std::atomic<size_t> next{0};
       host_parallel((unsigned)std::min(parse_threads, n), [&](unsigned) {
         for (size_t i; (i = next.fetch_add(1)) < n;)
-          screen(c, d, s, chain_ok, public_wires[b0 + i], n_public, proof_json[b0 + i], json_lens[b0 + i], true,
-                 items[i]);
+          screen(c, d, s, chain_ok, device_tr, public_wires[b0 + i], n_public, source(b0 + i), true, items[i]);
       });
     }
     clk.mark("proofs read and screened");
-    // I2 per chain proof, as the single call forms it (it may take the device and the pool).
+    // I2 per chain proof, as the single call forms it (it may take the device and the pool), unless the matrix
+    // launch below forms the chunk's at once.
     std::vector<size_t> chain;
     for (size_t i = 0; i < n; ++i) {
       if (!items[i].chain) continue;
-      const stark_status st = verify_interp2(ctx, c, items[i].pub, d, bx, items[i].interp2);
-      if (st != STARK_OK) return st;
+      if (!mat_i2) {
+        const stark_status st = verify_interp2(ctx, c, items[i].pub, d, bx, items[i].interp2);
+        if (st != STARK_OK) return st;
+      }
       chain.push_back(i);
     }
     clk.mark("boundary interpolants");
@@ -587,20 +879,69 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
           rt = F.pow_u64(rt, 4);
           dg = std::max<uint64_t>(dg / 4, 1);
         }
+        if (mat_i2) {
+          for (size_t j = 0; j < bx.size(); ++j) {
+            const uint32_t w = (uint32_t)c.pfi[2 * j];
+            memcpy(img + o_wire + 4 * j, &w, 4);
+          }
+          lagrange_basis(bx, img + o_mat);
+        }
       }
       {
         std::atomic<size_t> next{0};
         host_parallel((unsigned)std::min(parse_threads, nb), [&](unsigned) {
-          for (size_t k; (k = next.fetch_add(1)) < nb;) pack(s, d, c.os, p, nb, k, items[chain[k]], img);
+          for (size_t k; (k = next.fetch_add(1)) < nb;)
+            pack(s, d, c.os, p, nb, k, items[chain[k]], !device_tr, !mat_i2, img);
         });
       }
       clk.mark("openings packed");
-      const size_t from = consts_up ? base : 0;
-      STARK_HIP(ctx, hipMemcpyAsync(d_img + from, img + from, p.o_blocks + nb * s.block - from, hipMemcpyHostToDevice,
-                                    stream));
+      if (device_tr) {  // the call's constants once, then the blocks alone: the records are made on the device
+        if (!consts_up) STARK_HIP(ctx, hipMemcpyAsync(d_img, img, base, hipMemcpyHostToDevice, stream));
+        STARK_HIP(ctx, hipMemcpyAsync(d_img + p.o_blocks, img + p.o_blocks, nb * s.block, hipMemcpyHostToDevice, stream));
+      } else {
+        const size_t from = consts_up ? base : 0;
+        STARK_HIP(ctx, hipMemcpyAsync(d_img + from, img + from, p.o_blocks + nb * s.block - from, hipMemcpyHostToDevice,
+                                      stream));
+      }
       consts_up = true;
       uint8_t* const d_ok = d_img + p.o_ok;
       auto blocks = [](size_t lanes) { return dim3((unsigned)((lanes + kThreads - 1) / kThreads)); };
+      auto u = [](size_t x) { return (uint32_t)x; };
+      if (device_tr) {
+        TranscriptArgs A;
+        A.nb = u(nb);
+        A.layers = s.layers;
+        A.depth = s.depth;
+        A.prec = u(d.prec);
+        A.os = u(c.os);
+        A.skips = u(d.skips);
+        A.o_paths = u(p.o_paths);
+        A.o_rows = u(p.o_rows);
+        A.o_spots = u(p.o_spots);
+        A.o_blocks = u(p.o_blocks);
+        A.block = u(s.block);
+        A.o_aroot = u(s.o_aroot);
+        A.o_consts = u(s.o_consts);
+        A.o_i2 = u(s.o_i2);
+        A.o_main_leaf = u(s.o_main_leaf);
+        A.o_main_nodes = u(s.o_main_nodes);
+        A.o_l_leaf = u(s.o_l_leaf);
+        A.o_l_nodes = u(s.o_l_nodes);
+        for (uint32_t l = 0; l < kMaxLayers; ++l) {
+          const bool in = l < s.layers;
+          A.o_col_leaf[l] = in ? u(s.o_col_leaf[l]) : 0;
+          A.o_col_nodes[l] = in ? u(s.o_col_nodes[l]) : 0;
+          A.o_poly_leaf[l] = in ? u(s.o_poly_leaf[l]) : 0;
+          A.o_poly_nodes[l] = in ? u(s.o_poly_nodes[l]) : 0;
+        }
+        A.r2m = to_dev(F.from_canonical(F.one().v));
+        A.one = to_dev(F.one());
+        hipLaunchKernelGGL(verify_transcript_batch_kernel, dim3((unsigned)nb), dim3(kThreads), 0, stream, d_img, A);
+      }
+      if (mat_i2)
+        hipLaunchKernelGGL(verify_interp2_batch_kernel, dim3((unsigned)((bx.size() + kThreads - 1) / kThreads), (unsigned)nb),
+                           dim3(kThreads), 0, stream, d_img, (const fe*)(d_img + o_mat), (const uint32_t*)(d_img + o_wire),
+                           u(bx.size()), u(p.o_blocks), u(s.block), u(s.o_pub), u(s.o_i2));
       hipLaunchKernelGGL(verify_paths_batch_kernel, blocks(p.n_paths), dim3(kThreads), 0, stream, d_img,
                          (const PathRec*)(d_img + p.o_paths), (uint32_t)p.n_paths, d_ok);
       if (p.n_rows > 0) {
@@ -700,7 +1041,29 @@ stark_status stark_verify_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_ci
   STARK_HIP(ctx, hipSetDevice(ctx->device));
   std::vector<stark_status> sts(batch, STARK_OK);
   std::vector<uint32_t> why(batch, 0);
-  STARK_TRY(verify_r1cs_batch(ctx, circuit->c, public_wires, n_public, proof_json, json_lens, batch, sts.data(),
+  STARK_TRY(verify_r1cs_batch(ctx, circuit->c, public_wires, n_public, proof_json, json_lens, nullptr, batch,
+                              sts.data(), why.data()));
+  if (reasons) memcpy(reasons, why.data(), sizeof(uint32_t) * batch);
+  if (statuses) {
+    memcpy(statuses, sts.data(), sizeof(stark_status) * batch);
+    return STARK_OK;
+  }
+  for (uint32_t b = 0; b < batch; ++b)
+    if (sts[b] != STARK_OK) return sts[b];
+  return STARK_OK;
+}
+
+stark_status stark_verify_r1cs_circuit_batch_proofs(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
+                                                    const uint8_t* const* public_wires, size_t n_public,
+                                                    const stark_r1cs_proof* const* proofs, uint32_t batch,
+                                                    stark_status* statuses, uint32_t* reasons) {
+  if (!ctx || !circuit || !public_wires || !proofs || n_public == 0 || batch > 65535) return STARK_ERR_BAD_ARG;
+  if (batch == 0) return STARK_OK;  // (nothing to read, the handles included)
+  if (circuit->ctx != ctx || circuit->c.world != 1) return STARK_ERR_BAD_ARG;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<stark_status> sts(batch, STARK_OK);
+  std::vector<uint32_t> why(batch, 0);
+  STARK_TRY(verify_r1cs_batch(ctx, circuit->c, public_wires, n_public, nullptr, nullptr, proofs, batch, sts.data(),
                               why.data()));
   if (reasons) memcpy(reasons, why.data(), sizeof(uint32_t) * batch);
   if (statuses) {

@@ -188,6 +188,12 @@ _SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_char_p), _szp, ctypes.c_uint32,
                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
     "stark_ctx_set_verify_batch_limit": ([_vp, ctypes.c_size_t], ctypes.c_int),
+    "stark_verify_r1cs_circuit_batch_proofs": ([_vp, _vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t,
+                                                ctypes.POINTER(_vp), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
+                                                ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "stark_r1cs_proof_from_parts": ([_u8p, _u8p, _u8p, _vp, _vp, _vp, ctypes.c_size_t, _u8p, ctypes.c_size_t,
+                                     ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_ctx_set_verify_batch_transcript": ([_vp, ctypes.c_uint32], ctypes.c_int),
     "stark_verify_r1cs_bytes": ([_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                  ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
     "stark_group_create": ([ctypes.POINTER(ctypes.c_int), ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
@@ -352,6 +358,11 @@ class Context:
         (a larger batch runs as consecutive chunks); 0 = the default.  A cap below what the buffers hold frees
         them at once."""
         self.check(self.lib.stark_ctx_set_verify_batch_limit(self.h, int(nbytes)), "set_verify_batch_limit")
+
+    def set_verify_batch_transcript(self, mode: int):
+        """Who derives the indices, challenges and records of R1csCircuit.verify_batch's chain proofs: 1 the
+        host, 2 the device (one workgroup per proof), 0 the library's default.  Same statuses and reasons."""
+        self.check(self.lib.stark_ctx_set_verify_batch_transcript(self.h, int(mode)), "set_verify_batch_transcript")
 
     def memory(self) -> dict:
         """{'cached': bytes of cached tables, 'cache_limit': their cap, 'resident': all device bytes held}."""

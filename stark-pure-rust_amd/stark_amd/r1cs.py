@@ -88,6 +88,111 @@ class StarkProof:
         self.lib.stark_r1cs_proof_roots(self.h, m, l, a)
         return {"m_root": m.raw, "l_root": l.raw, "a_root": a.raw}
 
+    def branches(self, which: int) -> dict:
+        """stark_r1cs_proof_branches: main_branches (which = 0) or linear_comb_branches (1) as
+        {"leaves": k x leaf_len bytes, "nodes": k x depth x 32 bytes, "k", "leaf_len", "depth"}."""
+        k, ll, d = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        rc = self.lib.stark_r1cs_proof_branches(self.h, which, ctypes.byref(k), ctypes.byref(ll), ctypes.byref(d), None,
+                                                0, None, 0)
+        if rc != 0:
+            raise StarkError(rc, "stark_r1cs_proof_branches")
+        leaves = ctypes.create_string_buffer(max(k.value * ll.value, 1))
+        nodes = ctypes.create_string_buffer(max(k.value * d.value * 32, 1))
+        rc = self.lib.stark_r1cs_proof_branches(self.h, which, None, None, None, leaves, len(leaves), nodes, len(nodes))
+        if rc != 0:
+            raise StarkError(rc, "stark_r1cs_proof_branches")
+        return {"leaves": leaves.raw[:k.value * ll.value], "nodes": nodes.raw[:k.value * d.value * 32], "k": k.value,
+                "leaf_len": ll.value, "depth": d.value}
+
+    def fri_layers(self) -> list:
+        """The fri_proof through the stark_fri_proof_* accessors: a {"root2", "column", "poly"} dict per Middle
+        layer (column and poly as branches() gives them, 32-B leaves) and {"last": n x 32 bytes} for a Last."""
+        lib = self.lib
+        fri = lib.stark_r1cs_proof_fri(self.h)
+        out = []
+        for i in range(lib.stark_fri_proof_num_layers(fri)):
+            is_last = ctypes.c_int()
+            root2 = ctypes.create_string_buffer(32)
+            nc, cd, npl, pd, nl = (ctypes.c_size_t() for _ in range(5))
+            rc = lib.stark_fri_proof_layer_info(fri, i, ctypes.byref(is_last), root2, ctypes.byref(nc), ctypes.byref(cd),
+                                                ctypes.byref(npl), ctypes.byref(pd), ctypes.byref(nl))
+            if rc != 0:
+                raise StarkError(rc, "stark_fri_proof_layer_info")
+            sizes = [32 * nc.value, 32 * nc.value * cd.value, 32 * npl.value, 32 * npl.value * pd.value, 32 * nl.value]
+            bufs = [ctypes.create_string_buffer(max(n, 1)) for n in sizes]
+            rc = lib.stark_fri_proof_layer_data(fri, i, *[x for b in bufs for x in (b, len(b))])
+            if rc != 0:
+                raise StarkError(rc, "stark_fri_proof_layer_data")
+            cl, cn, pl, pn, lv = (b.raw[:n] for b, n in zip(bufs, sizes))
+            if is_last.value:
+                out.append({"last": lv})
+            else:
+                out.append({"root2": root2.raw,
+                            "column": {"leaves": cl, "nodes": cn, "k": nc.value, "leaf_len": 32, "depth": cd.value},
+                            "poly": {"leaves": pl, "nodes": pn, "k": npl.value, "leaf_len": 32, "depth": pd.value}})
+        return out
+
+    def parts(self) -> dict:
+        """Everything from_parts takes, read through the accessors."""
+        layers = self.fri_layers()
+        last = b"".join(x["last"] for x in layers if "last" in x)
+        return dict(self.roots(), main=self.branches(0), lcomb=self.branches(1),
+                    layers=[x for x in layers if "last" not in x], last=last)
+
+    @staticmethod
+    def parts_of_dict(proof: dict) -> dict:
+        """A parsed StarkProof (serde_json's dict) as from_parts' parts.  The openings of one set must have one
+        shape, and a Last value 32 bytes (StarkError(3) otherwise): a handle holds uniform arrays."""
+        def uniform(brs):
+            ll = len(brs[0]["leaf"]) if brs else 32
+            d = len(brs[0]["nodes"]) if brs else 0
+            if any(len(b["leaf"]) != ll or len(b["nodes"]) != d or any(len(n) != 32 for n in b["nodes"]) for b in brs):
+                raise StarkError(3, "StarkProof.from_parts", "openings of unequal shape")
+            return {"leaves": b"".join(bytes(b["leaf"]) for b in brs),
+                    "nodes": b"".join(bytes(n) for b in brs for n in b["nodes"]), "k": len(brs), "leaf_len": ll,
+                    "depth": d}
+        fri = proof["fri_proof"]
+        if not fri or "Last" not in fri[-1] or any("Middle" not in x for x in fri[:-1]):
+            raise StarkError(3, "StarkProof.from_parts", "Middle layers then one Last layer expected")
+        last = [bytes(v) for v in fri[-1]["Last"]["last"]]
+        if any(len(v) != 32 for v in last):
+            raise StarkError(3, "StarkProof.from_parts", "a Last value is not 32 bytes")
+        return {"m_root": bytes(proof["m_root"]), "l_root": bytes(proof["l_root"]), "a_root": bytes(proof["a_root"]),
+                "main": uniform(proof["main_branches"]), "lcomb": uniform(proof["linear_comb_branches"]),
+                "layers": [{"root2": bytes(x["Middle"]["root2"]), "column": uniform(x["Middle"]["column_branches"]),
+                            "poly": uniform(x["Middle"]["poly_branches"])} for x in fri[:-1]],
+                "last": b"".join(last)}
+
+    @classmethod
+    def from_parts(cls, parts, lib=None) -> "StarkProof":
+        """A handle over copies of a StarkProof's parts (stark_r1cs_proof_from_parts; host only): `parts` is what
+        parts() returns, or a parsed proof dict.  What R1csCircuit.verify_batch takes without any text."""
+        from .verify import _Branches, _FriLayer
+        lib = lib or load_library()
+        if "main_branches" in parts:
+            parts = cls.parts_of_dict(parts)
+
+        def br(b):
+            return _Branches(b["leaves"], b["nodes"], b["k"], b["leaf_len"], b["depth"])
+        for r in ("m_root", "l_root", "a_root"):
+            if len(parts[r]) != 32:
+                raise StarkError(3, "StarkProof.from_parts", f"{r} is not 32 bytes")
+        mb, lb = br(parts["main"]), br(parts["lcomb"])
+        mids = parts["layers"]
+        arr = (_FriLayer * max(len(mids), 1))()
+        for i, m in enumerate(mids):
+            if len(m["root2"]) != 32:
+                raise StarkError(3, "StarkProof.from_parts", "root2 is not 32 bytes")
+            arr[i] = _FriLayer(m["root2"], br(m["column"]), br(m["poly"]))
+        last = parts["last"]
+        h = _vp()
+        rc = lib.stark_r1cs_proof_from_parts(parts["m_root"], parts["l_root"], parts["a_root"], ctypes.byref(mb),
+                                             ctypes.byref(lb), ctypes.cast(arr, ctypes.c_void_p), len(mids), last,
+                                             len(last) // 32, ctypes.byref(h))
+        if rc != 0:
+            raise StarkError(rc, "stark_r1cs_proof_from_parts")
+        return cls(lib, h)
+
 
 def _sz(v) -> np.ndarray:
     a = np.ascontiguousarray(np.asarray(v, dtype=np.uint64).reshape(-1))
@@ -235,8 +340,15 @@ class R1csCircuit:
 
     def verify_batch(self, public_wires_list, proofs) -> list:
         """[(status, reasons)] of verify_circuit(public_wires, proof) for every pair, checked on the GPU through
-        one chain of launches (stark_amd.verify.verify_circuit_batch)."""
-        from .verify import verify_circuit_batch
+        one chain of launches (stark_amd.verify.verify_circuit_batch).  `proofs` holds texts or parsed dicts, or
+        StarkProof handles (verify_circuit_batch_proofs: no text on the way); None stands for a missing entry in
+        either.  A list that mixes handles with texts is StarkError(3)."""
+        from .verify import verify_circuit_batch, verify_circuit_batch_proofs
+        handles = [isinstance(p, StarkProof) for p in proofs]
+        if any(handles):
+            if not all(h or p is None for h, p in zip(handles, proofs)):
+                raise StarkError(3, "verify_batch", "StarkProof handles and proof texts in one list")
+            return verify_circuit_batch_proofs(self.ctx, self, public_wires_list, proofs)
         return verify_circuit_batch(self.ctx, self, public_wires_list, proofs)
 
 

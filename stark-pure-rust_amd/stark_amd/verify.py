@@ -139,6 +139,29 @@ def verify_circuit_batch(ctx: Context, circuit, public_wires_list, proofs) -> li
     return [(int(sts[b]), int(why[b])) for b in range(n)]
 
 
+def verify_circuit_batch_proofs(ctx: Context, circuit, public_wires_list, proofs) -> list:
+    """verify_circuit_batch for proofs held as StarkProof handles (stark_verify_r1cs_circuit_batch_proofs): no
+    text is rendered or parsed.  [(status, reasons)] per proof, equal to verify_circuit_batch's for the handles'
+    to_json(); None in place of a handle or of its public wires is that entry's status 3."""
+    n = len(proofs)
+    if len(public_wires_list) != n:
+        raise StarkError(3, "verify_circuit_batch_proofs", "one set of public wires per proof expected")
+    if n == 0:
+        return []
+    pubs = [None if w is None else _wire_bytes(w) for w in public_wires_list]
+    n_public = {len(p) // 32 for p in pubs if p is not None}
+    if len(n_public) > 1:
+        raise StarkError(3, "verify_circuit_batch_proofs", "public wire counts differ")
+    pub_ptrs = (ctypes.c_char_p * n)(*pubs)
+    hs = (ctypes.c_void_p * n)(*[None if p is None else p.h for p in proofs])
+    sts = (ctypes.c_int * n)()
+    why = (ctypes.c_uint32 * n)()
+    rc = ctx.lib.stark_verify_r1cs_circuit_batch_proofs(ctx.h, circuit.h, pub_ptrs, n_public.pop() if n_public else 0,
+                                                        hs, n, sts, why)
+    ctx.check(rc, "verify_circuit_batch_proofs")
+    return [(int(sts[b]), int(why[b])) for b in range(n)]
+
+
 def verify_with_wtns(ctx: Context, r1cs: bytes, wtns: bytes, proof) -> bool:
     """verify_with_file_path (run.rs:556-592) on file contents."""
     js = _json_bytes(proof)
