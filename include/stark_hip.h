@@ -44,8 +44,9 @@ extern "C" {
  * 8: stark_prove_r1cs_circuit_batch, stark_ctx_set_prove_batch_limit.
  * 9: stark_verify_r1cs_circuit_batch, stark_ctx_set_verify_batch_limit, STARK_VERIFY_FAIL_*.
  * 10: stark_verify_r1cs_circuit_batch_proofs, stark_r1cs_proof_from_parts,
- *     stark_ctx_set_verify_batch_transcript. */
-#define STARK_ABI_VERSION 10u
+ *     stark_ctx_set_verify_batch_transcript.
+ * 11: stark_interp_plan_*, stark_lagrange_interp_batch. */
+#define STARK_ABI_VERSION 11u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -235,6 +236,39 @@ stark_status stark_lagrange_interp(stark_ctx* ctx, const uint64_t* xs, const uin
  * and a gather instead of n Horner evaluations; the result is the same. */
 stark_status stark_lagrange_interp_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order,
                                           const uint64_t* exps, const uint64_t* ys, size_t n, uint64_t* out);
+
+/* An interpolation plan: everything of lagrange_interp (poly_utils.rs:409-439) that depends on the points
+ * alone -- the subproduct tree's transforms and inv(den_i) -- kept on the device and applied to `batch` value
+ * vectors at once.  No reference counterpart beyond calling lagrange_interp `batch` times over the same xs;
+ * every vector's result is that call's, a repeated x dropping out in the same way.  Building a plan takes the
+ * one host round trip (the batch inverse of the denominators); applying it is a fixed chain of launches.  A
+ * plan's device bytes count in stark_ctx_memory's resident_bytes while it lives.  It belongs to its context:
+ * stark_ctx_destroy releases the device memory of the plans still alive, after which a plan can only be freed
+ * (stark_interp_plan_free then frees the handle alone).  n = 0 gives a plan whose application is a no-op. */
+typedef struct stark_interp_plan stark_interp_plan;
+/* The plan of lagrange_interp(xs, .) (poly_utils.rs:409-439; no reference counterpart beyond calling it
+ * `batch` times). */
+stark_status stark_interp_plan_new(stark_ctx* ctx, const uint64_t* xs, size_t n, stark_interp_plan** out);
+/* The same for xs[i] = root^exps[i], as stark_lagrange_interp_domain (poly_utils.rs:409-439 over
+ * r1cs-stark/src/utils.rs:421-436's points; no reference counterpart beyond calling it `batch` times):
+ * exps[i] < 2^log_order, else STARK_ERR_BAD_ARG; STARK_ERR_BAD_ROOT for another root. */
+stark_status stark_interp_plan_new_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order,
+                                          const uint64_t* exps, size_t n, stark_interp_plan** out);
+/* Frees a plan (NULL is a no-op; no reference counterpart: poly_utils.rs:409-439 keeps nothing). */
+stark_status stark_interp_plan_free(stark_interp_plan* plan);
+/* lagrange_interp(xs, ys_b) for b < batch (poly_utils.rs:409-439, called `batch` times in the reference):
+ * ys is batch x n values, out batch x n coefficients, low degree first.  batch = 0 or n = 0 is a no-op.  The
+ * vectors are staged and run in consecutive chunks whose scratch stays under stark_ctx_set_prove_batch_limit's
+ * cap (3 x the padded point count x 32 B per vector), at least one vector each. */
+stark_status stark_interp_plan_apply(stark_interp_plan* plan, const uint64_t* ys, uint32_t batch, uint64_t* out);
+/* Device-resident form of the same (poly_utils.rs:409-439, `batch` times): asynchronous on `stream` (NULL =
+ * the context stream), no host synchronisation. */
+stark_status stark_interp_plan_apply_dev(stark_interp_plan* plan, const uint64_t* d_ys, uint32_t batch,
+                                         uint64_t* d_out, void* stream);
+/* lagrange_interp over one point set for `batch` value vectors (poly_utils.rs:409-439, called `batch` times
+ * in the reference): plan, apply, free. */
+stark_status stark_lagrange_interp_batch(stark_ctx* ctx, const uint64_t* xs, const uint64_t* ys, size_t n,
+                                         uint32_t batch, uint64_t* out);
 
 /* ---- DFT polynomial products (packages/fri/src/fft.rs) --------------------- */
 /* mul_polys<T>(a, b, root_of_unity) -> Vec<T> (fft.rs:381-395): a (la coefficients) and b (lb) zero-padded
@@ -429,7 +463,8 @@ stark_status stark_prove_r1cs_bytes(stark_ctx* ctx, const uint8_t* r1cs, size_t 
  * flags, permutation, public first uses, and the LDEs of K, F0-F2, IDX, PIDX);
  * stark_prove_r1cs_circuit then builds the witness columns and extends only S, P
  * and A.  The proof equals stark_prove_r1cs_bytes on the same bytes.  A circuit
- * is bound to the context that prepared it. */
+ * is bound to the context that prepared it: every call on it needs that context alive;
+ * stark_r1cs_circuit_free alone may also follow stark_ctx_destroy. */
 stark_status stark_r1cs_circuit_new(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len, stark_r1cs_circuit** out);
 void stark_r1cs_circuit_free(stark_r1cs_circuit* circuit);
 stark_status stark_prove_r1cs_circuit(stark_ctx* ctx, const stark_r1cs_circuit* circuit, const uint8_t* wtns,

@@ -163,6 +163,10 @@ constexpr uint32_t kDefaultVerifyTranscript = 1;
 
 }  // namespace stark
 
+namespace stark {
+struct InterpPlan;
+}
+
 struct stark_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -234,6 +238,10 @@ struct stark_ctx {
   // min(points, coefficients) from which multi-point evaluation descends the subproduct tree
   // (stark_ctx_set_multipoint_tree_min); 0: stark::kDefaultMultipointTreeMin.
   size_t multipoint_tree_min = 0;
+  // The interpolation plans that hold device memory on this context (poly.hip: interp_plan_build enters a plan,
+  // interp_plan_release takes it out).  stark_ctx_destroy frees what is left and empties those plans, so a handle
+  // or a circuit freed after its context finds nothing to free and touches no context memory.
+  std::vector<stark::InterpPlan*> interp_plans;
 };
 
 namespace stark {
@@ -342,6 +350,48 @@ struct DomainHint {
 size_t lagrange_scratch_elems(size_t n, const DomainHint* hint);
 stark_status lagrange_interp_device(stark_ctx* ctx, const fe* d_xs, const fe* d_ys, size_t n, fe* d_out, fe* mem,
                                     hipStream_t s, const DomainHint* hint, fe** z_out);
+// An interpolation plan: what lagrange_interp_device derives from the points alone, in a device buffer of its
+// own (ctx->poly is every other call's): the points' Montgomery images (n), inv_den[i] = R^2 / Z'(x_i) (n; 0 for
+// a repeated point: the product with a value as it is, any integer below 2^256, is c_i's Montgomery image) and the
+// kept transforms of the tree's `levels` NTT levels (2 N each).  Its bytes count in the context's resident bytes.
+// A plan that holds memory is entered in ctx->interp_plans by its address: it is not copied or moved while built.
+struct InterpPlan {
+  size_t n = 0, N = 0, bytes = 0;
+  uint32_t log_N = 0, levels = 0;
+  fe *mem = nullptr, *xs = nullptr, *inv_den = nullptr, *zt = nullptr;
+};
+// Builds the plan over the device points d_xs (canonical; hint as lagrange_interp_device's).  Takes ctx->poly for
+// its temporaries and the batch inverse's host round trip; the plan is complete when it returns.
+stark_status interp_plan_build(stark_ctx* ctx, const fe* d_xs, size_t n, const DomainHint* hint, InterpPlan& plan,
+                               hipStream_t s);
+// The same from host exponents: the points are root^exps[i] (root canonical, of order 2^log_order; exps checked).
+stark_status interp_plan_build_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order, const uint64_t* exps,
+                                      size_t n, InterpPlan& plan, hipStream_t s);
+// Frees the buffer and takes the plan out of ctx->interp_plans.  A plan never built, or emptied by its context's
+// destruction, holds nothing: a no-op that does not read ctx (which may be gone by then).
+void interp_plan_release(stark_ctx* ctx, InterpPlan& plan);
+// stark_ctx_destroy's part: frees every plan still entered and empties it.
+void interp_plans_release_all(stark_ctx* ctx);
+// Where a batch's values are: value i of proof b is the 32 bytes at base + b stride + 32 (index ? index[i] : i),
+// 16-B aligned, taken as they are (any integer below 2^256).
+struct InterpValues {
+  const uint8_t* base = nullptr;
+  uint64_t stride = 0;
+  const uint32_t* index = nullptr;
+};
+// Where the coefficients go: proof b's n coefficients at base + b stride (16-B aligned), canonical or (mont) as
+// Montgomery images, then zeros up to `fill` coefficients where fill > n.
+struct InterpOut {
+  uint8_t* base = nullptr;
+  uint64_t stride = 0;
+  bool mont = false;
+  uint64_t fill = 0;
+};
+// lagrange_interp of `batch` value vectors over the plan's points: one fixed chain of launches per chunk of
+// proofs (3 N elements of ctx->poly per proof, chunks under the context's prove-batch limit), no host
+// synchronisation.
+stark_status interp_plan_apply(stark_ctx* ctx, const InterpPlan& plan, const InterpValues& ys, uint32_t batch,
+                               const InterpOut& out, hipStream_t s);
 // g = 1 / h mod Y^(2^log_k) (canonical, 2^log_k coefficients into d_g; log_k >= 5) for h of hlen coefficients
 // (the rest zero) with h(0) != 0: h0_inv = the Montgomery image of 1 / h(0).  A schoolbook phase in one workgroup
 // up to the tree's leaf size, then Newton steps g <- g (2 - h g) by transforms on tree_twiddles' roots.  mem holds
@@ -667,6 +717,10 @@ struct PreparedCircuit {
   const uint8_t* flags = nullptr;
   const uint64_t* perm = nullptr;
   const uint32_t* slot_wire = nullptr;
+  // The interpolation plan over the boundary points g1^(w_k) (poly.hip), built by the first batched proof or
+  // verification that takes it (circuit_public_plan) and freed with the circuit, or with its context if that goes
+  // first.  mutable without a lock: a context, and with it its circuits, is driven by one thread at a time.
+  mutable InterpPlan pub_plan;
   // the circuit's columns with one witness' (circuit_witness: dt holds wit, comp and the public wires)
   TraceView view(const DevTrace& dt) const {
     return {{(const uint64_t*)coef, nullptr, nullptr, nullptr, (const uint64_t*)dt.wit, (const uint64_t*)dt.comp},
@@ -675,6 +729,10 @@ struct PreparedCircuit {
   }
 };
 stark_status circuit_build(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len, PreparedCircuit& c);
+// The circuit's plan over its boundary points x_k = g1^(pfi[2 k + 1]), g1 = g2^skips of order 2^log_steps (r1cs.hip):
+// the batched prover's and verifier's, whose points are the same.  Built on first use (one host round trip).
+stark_status circuit_public_plan(stark_ctx* ctx, const PreparedCircuit& c, const HostFp& g2, uint64_t skips,
+                                 uint32_t log_steps, hipStream_t s, const InterpPlan** out);
 // ---- batched proofs of one prepared circuit (stark_prove_r1cs_circuit_batch) ----
 // One witness of a batch, past circuit_witness's host checks: its values (field_size bytes each, value 0 first)
 // and the public wires (canonical limbs, 4 per wire).
@@ -837,6 +895,7 @@ struct stark_r1cs_circuit {
   stark_ctx* ctx = nullptr;
   stark::PreparedCircuit c;
   ~stark_r1cs_circuit() {
+    stark::interp_plan_release(ctx, c.pub_plan);
     if (c.arena.ptr) hipFree(c.arena.ptr);
     if (c.lde.ptr) hipFree(c.lde.ptr);
   }

@@ -19,6 +19,8 @@
 // N_parent = N_L Z_R + N_R Z_L (degree < 2^(l+1): no wrap), from the leaves' sum_i c_i Z_leaf / (X - x_i),
 // c_i = y_i / Z'(x_i) (the zero-preserving batch inverse: a repeated x has Z'(x) = 0 and drops out, as in
 // the reference, whose numerator then evaluates to 0).  The padded points carry c = 0.
+// An interpolation plan (InterpPlan) keeps what of this depends on the points alone -- the levels' transforms and
+// 1 / Z'(x_i) -- and goes up the tree for many value vectors at once, with no host round trip.
 //
 // The cut-over kLeafLog = 5.  One more level in the leaf kernel costs 2^l more products per point on one
 // dependent chain; one more NTT level costs about 3 (l + 1) products per point (three transforms of two
@@ -26,6 +28,8 @@
 // point counts this serves (public inputs: up to ~10^4) make a level's five launches dearer than the
 // 2^18 extra products of l = 5, and at l = 6 the leaf's chain (64 steps of three dependent products) would
 // be longer than those launches.  The choice is by this count, not by a measurement.
+#include <algorithm>
+
 #include "internal.h"
 
 namespace stark {
@@ -157,6 +161,83 @@ __global__ void poly_readout_kernel(const fe* __restrict__ top, uint64_t pad, ui
     v = (top_fix && i + pad == 0) ? fe_sub(t, v) : t;
   }
   fe_store(out + i, v);
+}
+
+// ---- the interpolation plan's kernels: one interpolation's way up for `batch` value vectors ----
+// Batched arrays are proof-major: proof b's N coefficients at nc + b N, its 2 N transform points at nt + 2 b N,
+// so a level's nodes of all proofs are one contiguous run for the batched transforms.
+
+// The plan's constants from the build's: xm[i] = x_i R (the Montgomery image) and inv2[i] = R^2 / Z'(x_i).
+__global__ void poly_plan_consts_kernel(const fe* __restrict__ xs, const fe* __restrict__ inv, uint64_t n, fe r2,
+                                        fe* __restrict__ xm, fe* __restrict__ inv2) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fe_store(xm + i, fe_mul(fe_load(xs + i), r2));
+  fe_store(inv2 + i, fe_mul(fe_mul(fe_load(inv + i), r2), r2));
+}
+
+// poly_leaf_kernel<true>'s recurrence for proof blockIdx.y: N <- N (X - x_i) + c_i Z, Z <- Z (X - x_i) with
+// c_(b,i) = y_(b,i) / Z'(x_i).  xm and inv2 are the plan's (poly_plan_consts_kernel): the value's 32 bytes as they
+// are (any integer below 2^256; the product's bounds allow one such operand, fe_mul_asm.inc) times inv2 is c's
+// Montgomery image, reduced.  Z is recomputed per proof and not stored: the levels above come from the plan's
+// kept transforms.
+__global__ __launch_bounds__(kPolyThreads) void poly_leaf_batch_kernel(const fe* __restrict__ xm,
+                                                                       const fe* __restrict__ inv2, InterpValues ys,
+                                                                       uint64_t n, uint64_t N, fe* __restrict__ n_out) {
+  __shared__ uint32_t xl[8 * kPolyThreads], zl[8 * kPolyThreads], cl[8 * kPolyThreads], nl[8 * kPolyThreads];
+  const uint32_t t = threadIdx.x, j = t & (kLeaf - 1), base = t - j;
+  const uint64_t g = (uint64_t)blockIdx.x * kPolyThreads + t, b = blockIdx.y;
+  fe x = fe_zero(), c = fe_zero();
+  if (g < n) {
+    x = fe_load(xm + g);
+    const uint64_t at = ys.index ? ys.index[g] : g;
+    c = fe_mul(fe_load(reinterpret_cast<const fe*>(ys.base + b * ys.stride) + at), fe_load(inv2 + g));
+  }
+  lds_put(xl, t, x);
+  lds_put(cl, t, c);
+  fe z = fe_zero(), nn = fe_zero();
+  if (j == 0) z.w[0] = 1;
+  for (uint32_t i = 0; i < kLeaf; ++i) {
+    lds_put(zl, t, z);
+    lds_put(nl, t, nn);
+    __syncthreads();
+    const fe xi = lds_get(xl, base + i);
+    const fe zp = j ? lds_get(zl, t - 1) : fe_zero();
+    const fe np = j ? lds_get(nl, t - 1) : fe_zero();
+    nn = fe_add(fe_sub(np, fe_mul(nn, xi)), fe_mul(z, lds_get(cl, base + i)));
+    z = fe_sub(zp, fe_mul(z, xi));
+    __syncthreads();
+  }
+  if (g < N) fe_store(n_out + b * N + g, nn);
+}
+
+// out[b][k][i] = N_(b,2k)^[i] Z_(2k+1)^[i] + N_(b,2k+1)^[i] Z_2k^[i] over all proofs (total = batch N lanes):
+// zt is the plan's level, shared by the proofs; nt and out are proof-major.  Adj as in poly_pair_comb_kernel.
+__global__ void poly_pair_comb_batch_kernel(const fe* __restrict__ zt, const fe* __restrict__ nt, uint32_t log_m,
+                                            uint32_t log_N, uint64_t total, Adj adj, fe r2, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t b = g >> log_N, gi = g & (((uint64_t)1 << log_N) - 1);
+  const uint64_t k = gi >> log_m, i = gi & (((uint64_t)1 << log_m) - 1);
+  const uint64_t l = ((2 * k) << log_m) + i, r = ((2 * k + 1) << log_m) + i;
+  const fe* ntb = nt + (b << (log_N + 1));
+  const fe d = (i & 1) ? adj.odd : adj.even;
+  const fe zl = fe_add(fe_load(zt + l), d), zr = fe_add(fe_load(zt + r), d);
+  const fe s = fe_add(fe_mul(fe_load(ntb + l), zr), fe_mul(fe_load(ntb + r), zl));
+  fe_store(out + g, fe_mul(s, r2));
+}
+
+// Proof blockIdx.y's coefficients out of the top: out_b[i] = nc_b[i + N - n] for i < n, canonical or (mont) as
+// Montgomery images, then zeros for n <= i < fill; out_b is at out.base + b out.stride.
+__global__ void poly_readout_batch_kernel(const fe* __restrict__ nc, uint64_t n, uint64_t N, InterpOut out, fe r2) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (i >= n && i >= out.fill) return;
+  fe v = fe_zero();
+  if (i < n) {
+    v = fe_load(nc + b * N + i + (N - n));
+    if (out.mont) v = fe_mul(v, r2);
+  }
+  fe_store(reinterpret_cast<fe*>(out.base + b * out.stride) + i, v);
 }
 
 // dz[k] = (k + 1) z[k + 1], k < n; dz[k] = 0 for n <= k < fill.
@@ -453,6 +534,159 @@ stark_status poly_domain_points(stark_ctx* ctx, const Twiddles& tw, const uint64
   return STARK_OK;
 }
 
+// ---- interpolation plans ----
+
+void interp_plan_release(stark_ctx* ctx, InterpPlan& plan) {
+  if (plan.mem) {  // (then the plan is entered in its context, which is alive: its destruction empties the plans)
+    hipFree(plan.mem);  // (waits for the device: a kernel of any stream may still read it)
+    auto& live = ctx->interp_plans;
+    live.erase(std::remove(live.begin(), live.end(), &plan), live.end());
+  }
+  plan = InterpPlan();
+}
+
+void interp_plans_release_all(stark_ctx* ctx) {
+  for (InterpPlan* p : ctx->interp_plans) {
+    hipFree(p->mem);
+    *p = InterpPlan();
+  }
+  ctx->interp_plans.clear();
+}
+
+// lagrange_interp_device up to its batch inverse, in ctx->poly, then the plan's own buffer from it.
+stark_status interp_plan_build(stark_ctx* ctx, const fe* d_xs, size_t n, const DomainHint* hint, InterpPlan& plan,
+                               hipStream_t s) {
+  plan = InterpPlan();
+  if (n == 0) return STARK_OK;
+  const PolyConsts pc = poly_consts();
+  PolyTree t;
+  poly_tree_plan(n, t);
+  if (hint && n > ((size_t)1 << hint->log_order)) hint = nullptr;  // Z' does not fit the domain: as the single call
+  const size_t dz_n = hint ? (size_t)1 << hint->log_order : n;
+  const size_t zt_elems = 2 * t.N * t.levels;
+  fe* own = nullptr;
+  const size_t bytes = (2 * n + zt_elems) * sizeof(fe);
+  if (hipMalloc((void**)&own, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return STARK_ERR_OOM;
+  }
+  plan.mem = own;
+  plan.bytes = bytes;
+  ctx->interp_plans.push_back(&plan);
+  plan.n = n;
+  plan.N = t.N;
+  plan.log_N = t.log_N;
+  plan.levels = t.levels;
+  plan.xs = own;
+  plan.inv_den = own + n;
+  plan.zt = own + 2 * n;
+  auto build = [&]() -> stark_status {
+    STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+    STARK_TRY(ensure_buf(ctx, ctx->poly, lagrange_scratch_elems(n, hint) * sizeof(fe)));
+    fe* mem = (fe*)ctx->poly.ptr;
+    fe* z = mem + poly_tree_elems(t) + 3 * t.N;  // lagrange_interp_device's layout
+    fe* dz = z + (n + 1);
+    fe* den = dz + dz_n;
+    fe* inv = den + n;
+    STARK_TRY(poly_tree_build(ctx, d_xs, t, mem, s));
+    if (zt_elems)  // (before the descent below, which reads the tree's t.zt but writes t.z only)
+      STARK_HIP(ctx, hipMemcpyAsync(plan.zt, t.zt, zt_elems * sizeof(fe), hipMemcpyDeviceToDevice, s));
+    STARK_TRY(poly_tree_zpoly(ctx, t, z, s));
+    hipLaunchKernelGGL(poly_deriv_kernel, dim3(grid_for(dz_n)), dim3(256), 0, s, (const fe*)z, (uint64_t)n,
+                       (uint64_t)dz_n, pc.r2, dz);
+    STARK_HIP(ctx, hipGetLastError());
+    if (hint) {
+      STARK_TRY(ntt_device(ctx, dz, hint->log_order, 1, *hint->tw, false, s));
+      hipLaunchKernelGGL(poly_gather_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const fe*)dz, hint->d_exps,
+                         (uint64_t)n, den);
+      STARK_HIP(ctx, hipGetLastError());
+    } else if (n >= (ctx->multipoint_tree_min ? ctx->multipoint_tree_min : kDefaultMultipointTreeMin) &&
+               n + t.N <= kMultipointTreeLimit) {
+      STARK_TRY(poly_tree_eval(ctx, t, d_xs, dz, n, den, inv + n, s));
+    } else {
+      STARK_TRY(eval_poly_device(ctx, dz, n, d_xs, n, den, s));
+    }
+    STARK_TRY(multi_inv_device(ctx, den, inv, n, s));
+    hipLaunchKernelGGL(poly_plan_consts_kernel, dim3(grid_for(n)), dim3(256), 0, s, d_xs, (const fe*)inv, (uint64_t)n,
+                       pc.r2, plan.xs, plan.inv_den);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(buf_release(ctx, ctx->poly, s));
+    // complete on return: the plan is applied on any stream, and d_xs is the caller's staging
+    STARK_HIP(ctx, hipStreamSynchronize(s));
+    return STARK_OK;
+  };
+  const stark_status st = build();
+  if (st != STARK_OK) interp_plan_release(ctx, plan);
+  return st;
+}
+
+stark_status interp_plan_build_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order, const uint64_t* exps,
+                                      size_t n, InterpPlan& plan, hipStream_t s) {
+  plan = InterpPlan();
+  if (n == 0) return STARK_OK;
+  if (log_order > 28) return STARK_ERR_BAD_LENGTH;
+  for (size_t i = 0; i < n; ++i)
+    if (exps[i] >> log_order) return STARK_ERR_BAD_ARG;
+  DomainHint hint;
+  STARK_TRY(get_twiddles(ctx, root, log_order, &hint.tw));
+  hint.log_order = log_order;
+  // staging: the points, then their exponents (the build returns synchronised: exps is read by then)
+  STARK_TRY(ensure_buf(ctx, ctx->io, n * (sizeof(fe) + sizeof(uint64_t))));
+  fe* d_xs = (fe*)ctx->io.ptr;
+  uint64_t* d_exps = (uint64_t*)(d_xs + n);
+  STARK_HIP(ctx, hipMemcpyAsync(d_exps, exps, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  hint.d_exps = d_exps;
+  STARK_TRY(poly_domain_points(ctx, *hint.tw, d_exps, n, d_xs, s));
+  return interp_plan_build(ctx, d_xs, n, &hint, plan, s);
+}
+
+// Proofs per chunk of an application: their scratch (nc: N, nt: 2 N per proof) stays under the prove-batch limit,
+// at least one proof; a grid's second coordinate and the transforms' 32-bit node count bound a chunk too.
+static size_t interp_plan_chunk(const stark_ctx* ctx, const InterpPlan& plan, uint32_t batch) {
+  const size_t limit = ctx->prove_batch_limit ? ctx->prove_batch_limit : kDefaultProveBatchLimit;
+  const size_t chunk = std::max<size_t>(1, limit / (3 * plan.N * sizeof(fe)));
+  return std::min<size_t>({chunk, batch, 65535, std::max<size_t>(1, ((size_t)1 << 31) / plan.N)});
+}
+
+stark_status interp_plan_apply(stark_ctx* ctx, const InterpPlan& plan, const InterpValues& ys, uint32_t batch,
+                               const InterpOut& out, hipStream_t s) {
+  if (batch == 0 || plan.n == 0) return STARK_OK;
+  const PolyConsts pc = poly_consts();
+  const size_t n = plan.n, N = plan.N;
+  const size_t chunk = interp_plan_chunk(ctx, plan, batch);
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  STARK_TRY(ensure_buf(ctx, ctx->poly, chunk * 3 * N * sizeof(fe)));
+  fe* nc = (fe*)ctx->poly.ptr;
+  fe* nt = nc + chunk * N;
+  for (uint32_t b0 = 0; b0 < batch; b0 += (uint32_t)chunk) {
+    const uint32_t B = (uint32_t)std::min<size_t>(chunk, batch - b0);
+    InterpValues y = ys;
+    y.base += (uint64_t)b0 * ys.stride;
+    InterpOut o = out;
+    o.base += (uint64_t)b0 * out.stride;
+    hipLaunchKernelGGL(poly_leaf_batch_kernel, dim3(grid_for(N), B), dim3(kPolyThreads), 0, s, (const fe*)plan.xs,
+                       (const fe*)plan.inv_den, y, (uint64_t)n, (uint64_t)N, nc);
+    STARK_HIP(ctx, hipGetLastError());
+    for (uint32_t lv = 0; lv < plan.levels; ++lv) {
+      const uint32_t log_m = kLeafLog + lv + 1;
+      const uint32_t nodes = (uint32_t)(N >> (log_m - 1));
+      const Twiddles *fwd, *tinv;
+      STARK_TRY(tree_twiddles(ctx, log_m, &fwd, &tinv));
+      STARK_TRY(ntt_device_from(ctx, nc, 1, nt, log_m, B * nodes, *fwd, false, s));
+      hipLaunchKernelGGL(poly_pair_comb_batch_kernel, dim3(grid_for((uint64_t)B * N)), dim3(256), 0, s,
+                         (const fe*)(plan.zt + 2 * N * lv), (const fe*)nt, log_m, plan.log_N, (uint64_t)B * N,
+                         level_adj(lv > 0), pc.r2, nc);
+      STARK_HIP(ctx, hipGetLastError());
+      STARK_TRY(ntt_device(ctx, nc, log_m, B * (nodes / 2), *tinv, true, s));
+    }
+    const uint64_t lanes = std::max<uint64_t>(n, out.fill);
+    hipLaunchKernelGGL(poly_readout_batch_kernel, dim3(grid_for(lanes), B), dim3(256), 0, s, (const fe*)nc, (uint64_t)n,
+                       (uint64_t)N, o, pc.r2);
+    STARK_HIP(ctx, hipGetLastError());
+  }
+  return buf_release(ctx, ctx->poly, s);
+}
+
 // a <- the 2^(log_k + 1) coefficients of a b, for a and b of 2^log_k coefficients each (no wrap); ta and tb
 // hold 2^(log_k + 1) elements each, the product lands in ta.
 static stark_status poly_full_product(stark_ctx* ctx, const fe* a, const fe* b, uint32_t log_k, fe* ta, fe* tb,
@@ -595,6 +829,12 @@ stark_status eval_multipoint_device(stark_ctx* ctx, const fe* d_poly, size_t deg
 
 using namespace stark;
 
+// An interpolation plan handle (stark_interp_plan_new): the plan and the context it lives on.
+struct stark_interp_plan {
+  stark_ctx* ctx = nullptr;
+  stark::InterpPlan p;
+};
+
 namespace {
 
 // mul_polys / div_polys (fft.rs:381-432): both inputs zero-padded to n = 2^log_n and transformed, the
@@ -707,6 +947,92 @@ stark_status stark_lagrange_interp_domain(stark_ctx* ctx, const uint64_t root[4]
                                           const uint64_t* exps, const uint64_t* ys, size_t n, uint64_t* out) {
   if (!ctx || !root || (n && (!exps || !ys || !out))) return STARK_ERR_BAD_ARG;
   return interp_host(ctx, nullptr, root, log_order, exps, ys, n, out);
+}
+
+stark_status stark_interp_plan_new(stark_ctx* ctx, const uint64_t* xs, size_t n, stark_interp_plan** out) {
+  if (!ctx || !out || (n && !xs)) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<stark_interp_plan> h(new stark_interp_plan);
+  h->ctx = ctx;
+  if (n) {
+    hipStream_t s = ctx->stream;
+    STARK_TRY(ensure_buf(ctx, ctx->io, n * sizeof(fe)));
+    STARK_HIP(ctx, hipMemcpyAsync(ctx->io.ptr, xs, n * sizeof(fe), hipMemcpyHostToDevice, s));
+    STARK_TRY(interp_plan_build(ctx, (const fe*)ctx->io.ptr, n, nullptr, h->p, s));
+  }
+  *out = h.release();
+  return STARK_OK;
+}
+
+stark_status stark_interp_plan_new_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order,
+                                          const uint64_t* exps, size_t n, stark_interp_plan** out) {
+  if (!ctx || !root || !out || (n && !exps)) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<stark_interp_plan> h(new stark_interp_plan);
+  h->ctx = ctx;
+  STARK_TRY(interp_plan_build_domain(ctx, root, log_order, exps, n, h->p, ctx->stream));
+  *out = h.release();
+  return STARK_OK;
+}
+
+stark_status stark_interp_plan_free(stark_interp_plan* plan) {
+  if (!plan) return STARK_OK;
+  if (plan->p.mem) (void)hipSetDevice(plan->ctx->device);
+  interp_plan_release(plan->ctx, plan->p);
+  delete plan;
+  return STARK_OK;
+}
+
+stark_status stark_interp_plan_apply_dev(stark_interp_plan* plan, const uint64_t* d_ys, uint32_t batch,
+                                         uint64_t* d_out, void* stream) {
+  if (!plan) return STARK_ERR_BAD_ARG;
+  const size_t n = plan->p.n;
+  if (batch == 0 || n == 0) return STARK_OK;
+  if (!d_ys || !d_out) return STARK_ERR_BAD_ARG;
+  stark_ctx* ctx = plan->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const InterpValues ys{(const uint8_t*)d_ys, n * sizeof(fe), nullptr};
+  const InterpOut o{(uint8_t*)d_out, n * sizeof(fe), false, 0};
+  return interp_plan_apply(ctx, plan->p, ys, batch, o, pick_stream(ctx, stream));
+}
+
+stark_status stark_interp_plan_apply(stark_interp_plan* plan, const uint64_t* ys, uint32_t batch, uint64_t* out) {
+  if (!plan) return STARK_ERR_BAD_ARG;
+  const size_t n = plan->p.n;
+  if (batch == 0 || n == 0) return STARK_OK;
+  if (!ys || !out) return STARK_ERR_BAD_ARG;
+  stark_ctx* ctx = plan->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  // staged a chunk of the application at a time (the values, the coefficients), each chunk behind the last on s
+  const size_t chunk = interp_plan_chunk(ctx, plan->p, batch);
+  STARK_TRY(ensure_buf(ctx, ctx->io, 2 * chunk * n * sizeof(fe)));
+  fe* d_ys = (fe*)ctx->io.ptr;
+  fe* d_out = d_ys + chunk * n;
+  const InterpValues v{(const uint8_t*)d_ys, n * sizeof(fe), nullptr};
+  const InterpOut o{(uint8_t*)d_out, n * sizeof(fe), false, 0};
+  for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+    const size_t B = std::min<size_t>(chunk, batch - b0), at = 4 * b0 * n;
+    STARK_HIP(ctx, hipMemcpyAsync(d_ys, ys + at, B * n * sizeof(fe), hipMemcpyHostToDevice, s));
+    STARK_TRY(interp_plan_apply(ctx, plan->p, v, (uint32_t)B, o, s));
+    STARK_HIP(ctx, hipMemcpyAsync(out + at, d_out, B * n * sizeof(fe), hipMemcpyDeviceToHost, s));
+  }
+  STARK_HIP(ctx, hipStreamSynchronize(s));
+  return STARK_OK;
+}
+
+stark_status stark_lagrange_interp_batch(stark_ctx* ctx, const uint64_t* xs, const uint64_t* ys, size_t n,
+                                         uint32_t batch, uint64_t* out) {
+  if (!ctx) return STARK_ERR_BAD_ARG;
+  if (n == 0 || batch == 0) return STARK_OK;
+  if (!xs || !ys || !out) return STARK_ERR_BAD_ARG;
+  stark_interp_plan* plan = nullptr;
+  STARK_TRY(stark_interp_plan_new(ctx, xs, n, &plan));
+  const stark_status st = stark_interp_plan_apply(plan, ys, batch, out);
+  stark_interp_plan_free(plan);
+  return st;
 }
 
 stark_status stark_eval_poly_multipoint(stark_ctx* ctx, const uint64_t* poly, size_t deg_plus_1, const uint64_t* xs,

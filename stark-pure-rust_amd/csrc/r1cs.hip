@@ -1016,6 +1016,21 @@ static stark_status public_points(stark_ctx* ctx, const HostFp& g2, uint64_t ski
   return poly_domain_points(ctx, *hint.tw, d_exps, n, d_xy, s);
 }
 
+stark_status circuit_public_plan(stark_ctx* ctx, const PreparedCircuit& c, const HostFp& g2, uint64_t skips,
+                                 uint32_t log_steps, hipStream_t s, const InterpPlan** out) {
+  if (!c.pub_plan.mem) {
+    const FieldHost& F = FieldHost::get();
+    const size_t n = c.pfi.size() / 2;
+    uint64_t g1c[4];
+    F.to_canonical(F.pow_u64(g2, skips), g1c);
+    std::vector<uint64_t> exps(n);
+    for (size_t i = 0; i < n; ++i) exps[i] = c.pfi[2 * i + 1];
+    STARK_TRY(interp_plan_build_domain(ctx, g1c, log_steps, exps.data(), n, c.pub_plan, s));
+  }
+  *out = &c.pub_plan;
+  return STARK_OK;
+}
+
 // Zb2's coefficients from the tree alone (a prepared circuit: no witness, no interpolation), scaled by R^-1
 // and zero-padded to steps, into coef.  staging: as public_points' h.
 static stark_status public_zb2_coefficients(stark_ctx* ctx, const HostFp& g2, uint64_t skips, uint32_t log_steps,
@@ -1424,15 +1439,13 @@ static stark_status stage_buffers(stark_ctx* ctx, const TraceView& v, Stage& st,
 
 // The column route's coefficients, before anything of the proof is enqueued on s (the interpolation's batch
 // inverse takes a host round trip): I2's into pubc + steps and, with_zb2 (no table gives 1 / Zb2), Zb2's
-// times R^-1 into pubc.  i2_dst non-null (a batch, whose proofs' I2 coefficients lie back to back; not with_zb2):
-// I2's coefficients, zero-padded to steps, go there and pubc is not touched.
+// times R^-1 into pubc.  (A batch's I2 coefficients come from the circuit's interpolation plan instead,
+// prove_r1cs_batch.)
 static stark_status public_coefficients(stark_ctx* ctx, const TraceView& v, const Stage& st, bool with_zb2,
-                                        hipStream_t s, fe* i2_dst = nullptr) {
+                                        hipStream_t s) {
   const uint64_t steps = st.d.steps;
   const size_t n = v.n_pfi;
-  if (i2_dst && with_zb2) return STARK_ERR_BAD_ARG;
-  if (i2_dst) STARK_HIP(ctx, hipMemsetAsync(i2_dst, 0, steps * sizeof(fe), s));
-  else STARK_HIP(ctx, hipMemsetAsync(st.pubc, 0, 2 * steps * sizeof(fe), s));
+  STARK_HIP(ctx, hipMemsetAsync(st.pubc, 0, 2 * steps * sizeof(fe), s));
   DomainHint hint;
   std::vector<uint64_t> staging;
   hint.log_order = st.d.log_steps;
@@ -1444,7 +1457,7 @@ static stark_status public_coefficients(stark_ctx* ctx, const TraceView& v, cons
   STARK_TRY(public_points(ctx, st.roots.g2, st.d.skips, st.d.log_steps, v.public_wires, v.pfi, n,
                           (uint64_t*)(xy + 2 * n), xy, hint, staging, s));
   fe* z = nullptr;  // (the interpolation synchronises s for its batch inverse: staging is free after it)
-  STARK_TRY(lagrange_interp_device(ctx, xy, xy + n, n, i2_dst ? i2_dst : st.pubc + steps, mem, s, &hint, &z));
+  STARK_TRY(lagrange_interp_device(ctx, xy, xy + n, n, st.pubc + steps, mem, s, &hint, &z));
   if (with_zb2) {
     hipLaunchKernelGGL(scale_rinv_kernel, dim3(blocks_for(n + 1)), dim3(256), 0, s, (const fe*)z, (uint64_t)(n + 1),
                        st.pubc);
@@ -1862,15 +1875,16 @@ static stark_status prove_r1cs(stark_ctx* ctx, const TraceView& v, const fe* pre
 // prove_r1cs with pre != nullptr for B witnesses through one chain of launches: every kernel of the chain takes
 // the proof as a grid coordinate (or runs over the proofs' arrays laid back to back where it is elementwise),
 // every per-proof array is batch-major (proof b at base + b * len), and the three trees of a proof are tree b of
-// three forests.  What stays per witness: the boundary constants and interpolants (host), and on the column
-// route I2's coefficients (one interpolation with its own host round trip per witness, ahead of the chain).
+// three forests.  What stays per witness: the boundary constants and interpolants (host).  On the column route
+// I2's coefficients of every proof come from one application of the circuit's interpolation plan (poly.hip
+// interp_plan_apply; the plan's one host round trip is the first call's), enqueued with the chain.
 // The chain itself keeps the single proof's one mid-pipeline round trip (the batch inverse's top level).
 
 // One chunk's working set, carved out of ctx->prove_batch.
 struct BatchBufs {
   WitnessBatchBufs wb;
   fe *wcopy, *pidx, *cols_sp, *cols_a, *nmr, *dnm, *tot, *dnm_c, *inv_dnm, *consts, *rows, *lvals;
-  fe *i2coef = nullptr, *i2col = nullptr;  // the column route
+  fe *i2coef = nullptr, *i2col = nullptr, *pubv = nullptr;  // the column route (pubv: the boundary points' values)
   uint64_t* acc_leaves;
   Transcript* d_tr;
 };
@@ -1902,6 +1916,7 @@ static void batch_carve(Carve& cv, BatchBufs& bb, const PreparedCircuit& c, cons
   if (pub_cols) {
     cv.add(&bb.i2coef, B * steps);
     cv.add(&bb.i2col, B * P);
+    cv.add(&bb.pubv, B * n_pfi);
   }
 }
 
@@ -1954,14 +1969,16 @@ static stark_status prove_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, c
     if (!f) STARK_TRY(stark_merkle_forest_new(ctx, &f));
   stark_merkle_forest *const f_acc = ctx->r1cs_forests[0], *const f_m = ctx->r1cs_forests[1],
                       *const f_l = ctx->r1cs_forests[2];
-  // Pinned slot 6: the transcript heads, the boundary constants, the witnesses' staging.
+  // Pinned slot 6: the transcript heads, the boundary constants, on the column route the boundary points' values,
+  // the witnesses' staging.
   constexpr size_t kTrHead = offsetof(Transcript, k_db);
   static_assert(kTrHead <= kBatchHeadBytes, "pinned slot 6 layout");
   const size_t heads_bytes = (size_t)B * kBatchHeadBytes, consts_bytes = (size_t)B * n_consts * sizeof(fe);
+  const size_t pubv_bytes = st.pub_cols ? (size_t)B * n_pfi * sizeof(fe) : 0;
   uint8_t* pin = nullptr;
-  STARK_TRY(ctx_pinned(ctx, 6, heads_bytes + consts_bytes + (size_t)B * c.n_wires * 32, (void**)&pin));
+  STARK_TRY(ctx_pinned(ctx, 6, heads_bytes + consts_bytes + pubv_bytes + (size_t)B * c.n_wires * 32, (void**)&pin));
   const uint8_t* const h_heads = pin;
-  bb.wb.h_stage = pin + heads_bytes + consts_bytes;
+  bb.wb.h_stage = pin + heads_bytes + consts_bytes + pubv_bytes;
   {  // per witness: the interpolants through its public wires' values (utils.rs:421-474)
     fe* const h_consts = (fe*)(pin + heads_bytes);
     HostFp x_last;
@@ -1972,9 +1989,18 @@ static stark_status prove_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, c
     }
     STARK_HIP(ctx, hipMemcpyAsync(bb.consts, h_consts, consts_bytes, hipMemcpyHostToDevice, s));
   }
-  if (st.pub_cols)  // per witness, each with the interpolation's host round trip
+  if (st.pub_cols) {  // I2's coefficients of every proof, zero-padded to steps: one upload, one plan application
+    const InterpPlan* plan = nullptr;
+    STARK_TRY(circuit_public_plan(ctx, c, st.roots.g2, skips, d.log_steps, s, &plan));
+    uint64_t* const h_pubv = (uint64_t*)(pin + heads_bytes + consts_bytes);
     for (uint32_t b = 0; b < B; ++b)
-      STARK_TRY(public_coefficients(ctx, batch_view(c, *w[b]), st, false, s, bb.i2coef + (size_t)b * steps));
+      for (size_t i = 0; i < n_pfi; ++i)
+        memcpy(h_pubv + 4 * ((size_t)b * n_pfi + i), w[b]->public_wires.data() + 4 * v.pfi[2 * i], 32);
+    STARK_HIP(ctx, hipMemcpyAsync(bb.pubv, h_pubv, pubv_bytes, hipMemcpyHostToDevice, s));
+    const InterpValues ys{(const uint8_t*)bb.pubv, n_pfi * sizeof(fe), nullptr};
+    const InterpOut o{(uint8_t*)bb.i2coef, steps * sizeof(fe), false, steps};
+    STARK_TRY(interp_plan_apply(ctx, *plan, ys, B, o, s));
+  }
   // The constraint kernel's shared arguments and the host-built constants (into tr[0], then every transcript's).
   st.cols = bb.cols_sp;
   st.consts = bb.consts;

@@ -18,7 +18,8 @@
 // Two more launches may precede the three: verify_transcript_batch_kernel derives a chain proof's indices,
 // challenges and records from the roots in its block, one workgroup per proof, where the context asks for the
 // device's transcript (the host then uploads openings only); verify_interp2_batch_kernel forms every chain proof's
-// I2 from the Lagrange basis of the circuit's boundary points where that matrix is small enough.
+// I2 from the Lagrange basis of the circuit's boundary points where that matrix is small enough; from the
+// verification threshold on, one application of the circuit's interpolation plan (poly.hip) forms them instead.
 #include <string.h>
 
 #include <algorithm>
@@ -635,7 +636,8 @@ void put_branches(uint8_t* leaves, uint8_t* nodes, const std::vector<Branch>& v)
 // Chain proof k of nb: its block and its records.  The path records are class-major -- main, L, then each
 // layer's polynomial and column openings -- so that equal shapes are side by side; rows are layer-major.
 // host_tr: the host writes the constants and the records (else verify_transcript_batch_kernel does, and nothing
-// of them is written or uploaded); host_i2: the host writes I2's coefficients (else verify_interp2_batch_kernel).
+// of them is written or uploaded); host_i2: the host writes I2's coefficients (else verify_interp2_batch_kernel
+// or the circuit's interpolation plan does).
 void pack(const Shape& s, const VerifyDomain& d, size_t os, const ChunkPlan& p, size_t nb, size_t k, const Item& it,
           bool host_tr, bool host_i2, uint8_t* img) {
   const size_t blk = p.o_blocks + k * s.block;
@@ -799,8 +801,12 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
                                         (size_t)3 << 30);
   // I2 of a chunk's proofs by one launch over the Lagrange basis of the circuit's boundary points
   // (verify_interp2_batch_kernel): below the threshold from which verify_interp2 interpolates on the GPU, and
-  // where the n_b x n_b matrix stays under a quarter of the cap.  Else per proof, by verify_interp2.
-  bool mat_i2 = false;
+  // where the n_b x n_b matrix stays under a quarter of the cap.  From that threshold on, where verify_interp2
+  // would interpolate on the GPU (fewer points than steps), by one application of the circuit's interpolation
+  // plan per chunk (poly.hip interp_plan_apply), which reads the wires' values out of the blocks and writes every
+  // I2 slot.  Else per proof, by verify_interp2 (the host's lagrange_interp).
+  bool mat_i2 = false, plan_i2 = false;
+  const InterpPlan* i2_plan = nullptr;
   if (chain_ok) {
     bx = verify_boundary_points(c, d);
     x_last = F.pow_u64(d.g2, (d.steps - 1) * d.skips);
@@ -813,7 +819,9 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
     const size_t n_b = bx.size(), col_min = ctx->public_column_min ? ctx->public_column_min : kDefaultVerifyColumnMin;
     mat_i2 = n_b > 0 && n_b < col_min && 32 * n_b * n_b <= limit / 4;  // (n_b < 2^21: the product fits)
     for (size_t i = 0; mat_i2 && i < n_b; ++i) mat_i2 = c.pfi[2 * i] < c.n_public;
-    o_mat = (o_wire + (mat_i2 ? 4 * n_b : 0) + 31) & ~(size_t)31;
+    plan_i2 = n_b > 0 && n_b >= col_min && n_b < d.steps;
+    for (size_t i = 0; plan_i2 && i < n_b; ++i) plan_i2 = c.pfi[2 * i] < c.n_public && c.pfi[2 * i + 1] < d.steps;
+    o_mat = (o_wire + (mat_i2 || plan_i2 ? 4 * n_b : 0) + 31) & ~(size_t)31;
     base = align256(o_mat + (mat_i2 ? 32 * n_b * n_b : 0));
   }
   const size_t per_chunk = chain_ok ? std::max<size_t>(1, limit / s.staged()) : batch;
@@ -853,7 +861,7 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
     std::vector<size_t> chain;
     for (size_t i = 0; i < n; ++i) {
       if (!items[i].chain) continue;
-      if (!mat_i2) {
+      if (!mat_i2 && !plan_i2) {
         const stark_status st = verify_interp2(ctx, c, items[i].pub, d, bx, items[i].interp2);
         if (st != STARK_OK) return st;
       }
@@ -879,19 +887,19 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
           rt = F.pow_u64(rt, 4);
           dg = std::max<uint64_t>(dg / 4, 1);
         }
-        if (mat_i2) {
+        if (mat_i2 || plan_i2)
           for (size_t j = 0; j < bx.size(); ++j) {
             const uint32_t w = (uint32_t)c.pfi[2 * j];
             memcpy(img + o_wire + 4 * j, &w, 4);
           }
-          lagrange_basis(bx, img + o_mat);
-        }
+        if (mat_i2) lagrange_basis(bx, img + o_mat);
+        if (plan_i2) STARK_TRY(circuit_public_plan(ctx, c, d.g2, d.skips, log_steps, stream, &i2_plan));
       }
       {
         std::atomic<size_t> next{0};
         host_parallel((unsigned)std::min(parse_threads, nb), [&](unsigned) {
           for (size_t k; (k = next.fetch_add(1)) < nb;)
-            pack(s, d, c.os, p, nb, k, items[chain[k]], !device_tr, !mat_i2, img);
+            pack(s, d, c.os, p, nb, k, items[chain[k]], !device_tr, !mat_i2 && !plan_i2, img);
         });
       }
       clk.mark("openings packed");
@@ -942,6 +950,12 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
         hipLaunchKernelGGL(verify_interp2_batch_kernel, dim3((unsigned)((bx.size() + kThreads - 1) / kThreads), (unsigned)nb),
                            dim3(kThreads), 0, stream, d_img, (const fe*)(d_img + o_mat), (const uint32_t*)(d_img + o_wire),
                            u(bx.size()), u(p.o_blocks), u(s.block), u(s.o_pub), u(s.o_i2));
+      if (plan_i2) {  // the wires' bytes as they are, gathered through the wire indices; Montgomery images out
+        STARK_HIP(ctx, hipGetLastError());
+        const InterpValues ys{d_img + p.o_blocks + s.o_pub, s.block, (const uint32_t*)(d_img + o_wire)};
+        const InterpOut o{d_img + p.o_blocks + s.o_i2, s.block, true, 0};
+        STARK_TRY(interp_plan_apply(ctx, *i2_plan, ys, (uint32_t)nb, o, stream));
+      }
       hipLaunchKernelGGL(verify_paths_batch_kernel, blocks(p.n_paths), dim3(kThreads), 0, stream, d_img,
                          (const PathRec*)(d_img + p.o_paths), (uint32_t)p.n_paths, d_ok);
       if (p.n_rows > 0) {

@@ -73,6 +73,13 @@ _SIGNATURES = {
     "stark_lagrange_interp": ([_vp, _u64p, _u64p, ctypes.c_size_t, _u64p], ctypes.c_int),
     "stark_lagrange_interp_domain": ([_vp, _u64p, ctypes.c_uint32, _u64p, _u64p, ctypes.c_size_t, _u64p],
                                      ctypes.c_int),
+    "stark_interp_plan_new": ([_vp, _u64p, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_interp_plan_new_domain": ([_vp, _u64p, ctypes.c_uint32, _u64p, ctypes.c_size_t, ctypes.POINTER(_vp)],
+                                     ctypes.c_int),
+    "stark_interp_plan_free": ([_vp], ctypes.c_int),
+    "stark_interp_plan_apply": ([_vp, _u64p, ctypes.c_uint32, _u64p], ctypes.c_int),
+    "stark_interp_plan_apply_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
+    "stark_lagrange_interp_batch": ([_vp, _u64p, _u64p, ctypes.c_size_t, ctypes.c_uint32, _u64p], ctypes.c_int),
     "stark_mul_polys": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p],
                         ctypes.c_int),
     "stark_div_polys": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p],
@@ -291,6 +298,12 @@ def _limbs(x) -> np.ndarray:
 
 def _elems(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+
+
+def _batch_values(ys, n: int) -> np.ndarray:
+    """ys as a C-contiguous (batch, n, 4) array (n = 0: one empty vector per entry of ys)."""
+    y = np.ascontiguousarray(ys, dtype=np.uint64)
+    return y.reshape(-1, n, 4) if n else y.reshape(len(y), 0, 4)
 
 
 def _out_array(out, log_n: int) -> np.ndarray:
@@ -539,6 +552,36 @@ class Context:
                                                          _p64(e), _p64(y), len(y), _p64(out)), "lagrange_interp")
         return out
 
+    def interp_plan(self, xs, root_of_unity=None, log_order_of_root: int = 0) -> "InterpPlan":
+        """What lagrange_interp (poly_utils.rs:409-439) derives from the points alone, kept on the device for
+        many value vectors: InterpPlan.apply(ys) interpolates a (batch, n, 4) array at once.  With
+        root_of_unity, `xs` is a list of exponents, as in lagrange_interp."""
+        h = _vp()
+        if root_of_unity is None:
+            x = _elems(xs)
+            self.check(self.lib.stark_interp_plan_new(self.h, _p64(x), len(x), ctypes.byref(h)), "interp_plan")
+            return InterpPlan(self, h, len(x))
+        e = np.ascontiguousarray(xs, dtype=np.uint64).reshape(-1)
+        self.check(self.lib.stark_interp_plan_new_domain(self.h, _p64(_limbs(root_of_unity)), log_order_of_root,
+                                                         _p64(e), len(e), ctypes.byref(h)), "interp_plan")
+        return InterpPlan(self, h, len(e))
+
+    def lagrange_interp_batch(self, xs, ys, root_of_unity=None, log_order_of_root: int = 0) -> np.ndarray:
+        """[lagrange_interp(xs, y) for y in ys] (poly_utils.rs:409-439) for ys of shape (batch, len(xs), 4): one
+        plan over the points, one application, the same coefficients."""
+        if root_of_unity is None:
+            x = _elems(xs)
+            y = _batch_values(ys, len(x))
+            out = np.empty_like(y)
+            self.check(self.lib.stark_lagrange_interp_batch(self.h, _p64(x), _p64(y), len(x), y.shape[0], _p64(out)),
+                       "lagrange_interp_batch")
+            return out
+        plan = self.interp_plan(xs, root_of_unity, log_order_of_root)
+        try:
+            return plan.apply(ys)
+        finally:
+            plan.close()
+
     def mul_polys(self, a, b, root_of_unity, log_order_of_root: int) -> np.ndarray:
         """fft.rs:381-395: the cyclic product of length 2^log_order_of_root."""
         return self._mul_div(self.lib.stark_mul_polys, "mul_polys", a, b, root_of_unity, log_order_of_root)
@@ -655,6 +698,40 @@ class Context:
         hs = (_vp * max(batch, 1))()
         self.check(fn(self.h, values, n, batch, _p64(_limbs(root)), max_deg_plus_1, excl, hs), "prove_low_degree_batch")
         return [FriProofList(self.lib, _vp(hs[b])) for b in range(batch)]
+
+
+class InterpPlan:
+    """An interpolation plan over fixed points (Context.interp_plan), held by the library; close() frees it.
+    Closing its context first releases the plan's device memory; close() then frees the handle alone."""
+
+    def __init__(self, ctx, h, n: int):
+        self.ctx = ctx
+        self.h = h
+        self.n = n
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.stark_interp_plan_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, ys) -> np.ndarray:
+        """ys of shape (batch, n, 4) -> the coefficients, low degree first, in the same shape."""
+        y = _batch_values(ys, self.n)
+        out = np.empty_like(y)
+        self.ctx.check(self.ctx.lib.stark_interp_plan_apply(self.h, _p64(y), y.shape[0], _p64(out)),
+                       "interp_plan_apply")
+        return out
+
+    def apply_dev(self, d_ys: int, batch: int, d_out: int, stream: int = 0) -> None:
+        """The same on device buffers (batch x n elements each), asynchronous on `stream` (0 = the context's)."""
+        self.ctx.check(self.ctx.lib.stark_interp_plan_apply_dev(self.h, d_ys, batch, d_out, stream or None),
+                       "interp_plan_apply_dev")
 
 
 class FriProofList:
