@@ -31,7 +31,8 @@ def fe(b) -> int:
 
 
 def inv(x: int) -> int:
-    return pow(x, P - 2, P)
+    x %= P
+    return pow(x, -1, P) if x else 0  # (x^(p-2), without the 254 squarings)
 
 
 def get_pseudorandom_indices(seed: bytes, modulus: int, count: int, exclude: int) -> list:
@@ -47,16 +48,21 @@ def get_pseudorandom_indices(seed: bytes, modulus: int, count: int, exclude: int
     return [(w % real) + 1 + (w % real) // (exclude - 1) for w in words]
 
 
+def path_root(index: int, leaf: bytes, nodes) -> bytes:
+    """Proof::validate's walk (commitment/src/merkle_tree.rs:25-43): the root that one opening reaches."""
+    cur = blake(bytes(leaf))
+    tmp = index
+    for node in nodes:
+        cur = blake(cur + bytes(node)) if tmp % 2 == 0 else blake(bytes(node) + cur)
+        tmp //= 2
+    return cur
+
+
 def verify_multi_branch(root, indices, proofs) -> list:
     """commitment/src/merkle_tree.rs:25-58"""
     out = []
     for index, prf in zip(indices, proofs):
-        cur = blake(bytes(prf["leaf"]))
-        tmp = index
-        for node in prf["nodes"]:
-            cur = blake(cur + bytes(node)) if tmp % 2 == 0 else blake(bytes(node) + cur)
-            tmp //= 2
-        assert cur == bytes(root), "merkle branch does not reach the root"
+        assert path_root(index, prf["leaf"], prf["nodes"]) == bytes(root), "merkle branch does not reach the root"
         out.append(bytes(prf["leaf"]))
     return out
 
@@ -113,6 +119,35 @@ def _interp4_at(xs4, ys4, x) -> int:
     return acc
 
 
+def quartic_roots(w: int, rou_deg: int) -> list:
+    """The four fourth roots of one for a root of unity w of order rou_deg (fri.rs:263-268)."""
+    return [1, pow(w, rou_deg // 4, P), pow(w, rou_deg // 2, P), pow(w, rou_deg * 3 // 4, P)]
+
+
+def fri_row_holds(w: int, quartic: list, y: int, row: list, column, special_x: int) -> bool:
+    """One row of one Middle layer (fri.rs:318-345): the cubic through (w^y quartic[j], row[j]) at special_x
+    against the column value; row and column are the leaves' bytes."""
+    x1 = pow(w, y, P)
+    xc = [q * x1 % P for q in quartic]
+    return _interp4_at(xc, [fe(v) for v in row], special_x) == fe(column)
+
+
+def last_layer_root_holds(last: list, merkle_root_b: bytes) -> bool:
+    """fri.rs:367-375: the tree over the Last values as they are."""
+    return merkle_root(last) == merkle_root_b
+
+
+def last_layer_degree_holds(last: list, w: int, rou_deg: int, max_deg_plus_1: int, exclude: int) -> bool:
+    """fri.rs:377-401: the values off the excluded points lie on one polynomial of max_deg_plus_1 coefficients."""
+    dec = [fe(v) for v in last]
+    xs = [pow(w, i, P) for i in range(rou_deg)]
+    pts = [p for p in range(len(last)) if exclude == 0 or p % exclude != 0]
+    rest = pts[max_deg_plus_1:]
+    pts = pts[:max_deg_plus_1]
+    poly = lagrange_interp([xs[p] for p in pts], [dec[p] for p in pts])
+    return all(eval_poly_at(poly, xs[p]) == dec[p] for p in rest)
+
+
 def verify_low_degree_proof(merkle_root_b: bytes, root_of_unity_v: int, proof: list, max_deg_plus_1: int,
                             exclude: int) -> bool:
     """fri.rs:244-404"""
@@ -122,7 +157,7 @@ def verify_low_degree_proof(merkle_root_b: bytes, root_of_unity_v: int, proof: l
         rou_deg *= 2
         t = t * t % P
     w = root_of_unity_v
-    quartic = [1, pow(w, rou_deg // 4, P), pow(w, rou_deg // 2, P), pow(w, rou_deg * 3 // 4, P)]
+    quartic = quartic_roots(w, rou_deg)
     for prf in proof[:-1]:
         assert "Middle" in prf, "FRI proofs must consist of FriProof::Middle except the last element."
         m = prf["Middle"]
@@ -133,10 +168,8 @@ def verify_low_degree_proof(merkle_root_b: bytes, root_of_unity_v: int, proof: l
         column_values = verify_multi_branch(root2, ys, m["column_branches"])
         poly_values = verify_multi_branch(merkle_root_b, poly_positions, m["poly_branches"])
         for i, y in enumerate(ys):
-            x1 = pow(w, y, P)
-            xc = [q * x1 % P for q in quartic]
-            row = [fe(poly_values[i * 4 + j]) for j in range(4)]
-            assert _interp4_at(xc, row, special_x) == fe(column_values[i]), "FRI column check failed"
+            assert fri_row_holds(w, quartic, y, poly_values[i * 4:i * 4 + 4], column_values[i], special_x), \
+                "FRI column check failed"
         merkle_root_b = root2
         w = pow(w, 4, P)
         max_deg_plus_1 //= 4
@@ -145,15 +178,8 @@ def verify_low_degree_proof(merkle_root_b: bytes, root_of_unity_v: int, proof: l
     assert "Last" in proof[-1], "The last element of FRI proofs must be FriProof::Last."
     last = [bytes(v) for v in proof[-1]["Last"]["last"]]
     assert len(last) > max_deg_plus_1
-    dec = [fe(v) for v in last]
-    assert merkle_root(last) == merkle_root_b, "FRI last-layer root mismatch"
-    xs = [pow(w, i, P) for i in range(rou_deg)]
-    pts = [p for p in range(len(last)) if exclude == 0 or p % exclude != 0]
-    rest = pts[max_deg_plus_1:]
-    pts = pts[:max_deg_plus_1]
-    poly = lagrange_interp([xs[p] for p in pts], [dec[p] for p in pts])
-    for p in rest:
-        assert eval_poly_at(poly, xs[p]) == dec[p], "FRI last-layer degree check failed"
+    assert last_layer_root_holds(last, merkle_root_b), "FRI last-layer root mismatch"
+    assert last_layer_degree_holds(last, w, rou_deg, max_deg_plus_1, exclude), "FRI last-layer degree check failed"
     return True
 
 
@@ -164,6 +190,43 @@ def _log2_ceil(v: int) -> int:
         t //= 2
         lv += 1
     return lv
+
+
+def spot_rows(j: int, precision: int, skips: int, original_steps: int) -> list:
+    """The four main-tree rows opened for position j (verify.rs:86-101): x, x / g1, x g1^(os/3), x g1^(2os/3)."""
+    return [j, (j + precision - skips) % precision, (j + original_steps // 3 * skips) % precision,
+            (j + 2 * original_steps // 3 * skips) % precision]
+
+
+def challenges(m_root: bytes, a_root: bytes, precision: int):
+    """r from a_root and k from m_root (verify.rs:159-175)."""
+    rnd = get_pseudorandom_indices(a_root, precision, 24, 0)
+    r = [int.from_bytes(b"".join(v.to_bytes(4, "big") for v in rnd[8 * c:8 * c + 8]), "little") % P
+         for c in range(3)]
+    kk = [1] + [int.from_bytes(blake(m_root + bytes([i])), "big") % P for i in range(1, 11)]
+    return r, kk
+
+
+def spot_equalities(main4: list, l_leaf, xst: int, k_x: int, f0: int, f1: int, f2: int, idx: int, pidx: int,
+                    r: list, kk: list, zb2: int, i2: int, zb3: int, i3: int) -> list:
+    """One position's six equalities (verify.rs:185-254) as (name, the reference's assertion, lhs, rhs), in the
+    reference's order.  main4: the position's four 256-byte main leaves; xst = x^steps; the circuit's columns,
+    Zb2, I2, Zb3 = x - x_last and I3 at x."""
+    b = [[fe(main4[q][32 * c:32 * c + 32]) for c in range(8)] for q in range(4)]
+    p_x, a_x, s_x, d1, d2, d3, b2, b3 = b[0]
+    p_prev, a_prev = b[1][0], b[1][1]
+    p_w, p_2w = b[2][0], b[3][0]
+    z = (xst - 1) % P
+    nmr = (r[0] + r[1] * idx + r[2] * s_x) % P
+    dnm = (r[0] + r[1] * pidx + r[2] * s_x) % P
+    want = (kk[0] * d1 + kk[1] * d2 + kk[2] * d3 + kk[3] * p_x + kk[4] * p_x * xst + kk[5] * b2
+            + kk[6] * b2 * xst + kk[7] * b3 + kk[8] * b3 * xst + kk[9] * a_x + kk[10] * s_x) % P
+    return [("Q1", "Q1 = Z * D1", f0 * (p_x - f1 * p_prev - k_x * s_x) % P, z * d1 % P),
+            ("Q2", "Q2 = Z * D2", f2 * (p_2w - p_x * p_w) % P, z * d2 % P),
+            ("Q3", "Q3 = Z * D3", (a_x * dnm - a_prev * nmr) % P, z * d3 % P),
+            ("B2", "S - I2 = Zb2 * B2", (s_x - i2) % P, zb2 * b2 % P),
+            ("B3", "A - I3 = Zb3 * B3", (a_x - i3) % P, zb3 * b3 % P),
+            ("L", "linear combination", fe(l_leaf), want)]
 
 
 def verify_r1cs_proof(orc: Oracle, proof, public_wires, public_first_indices, permuted_indices, coefficients,
@@ -197,8 +260,7 @@ def verify_r1cs_proof(orc: Oracle, proof, public_wires, public_first_indices, pe
     positions = get_pseudorandom_indices(l_root, precision, SPOT_CHECK_SECURITY_FACTOR, skips)
     aug = []
     for j in positions:
-        aug += [j, (j + precision - skips) % precision, (j + original_steps // 3 * skips) % precision,
-                (j + 2 * original_steps // 3 * skips) % precision]
+        aug += spot_rows(j, precision, skips, original_steps)
     main_leaves = verify_multi_branch(m_root, aug, proof["main_branches"])
     l_leaves = verify_multi_branch(l_root, positions, proof["linear_comb_branches"])
     # Z(x) = x^steps - 1 evaluated at the spot-check points (verify.rs:121-122)
@@ -213,31 +275,15 @@ def verify_r1cs_proof(orc: Oracle, proof, public_wires, public_first_indices, pe
     x_last = xs[(steps - 1) * skips]
     interp3 = lagrange_interp([xs[precision - skips]], [1])
     # r and k (verify.rs:159-175)
-    rnd = get_pseudorandom_indices(a_root, precision, 24, 0)
-    r = [int.from_bytes(b"".join(v.to_bytes(4, "big") for v in rnd[8 * c:8 * c + 8]), "little") % P
-         for c in range(3)]
-    kk = [1] + [int.from_bytes(blake(m_root + bytes([i])), "big") % P for i in range(1, 11)]
+    r, kk = challenges(m_root, a_root, precision)
     for i, pos in enumerate(positions):
         x = xs[pos]
-        b = [[fe(main_leaves[i * 4 + q][32 * c:32 * c + 32]) for c in range(8)] for q in range(4)]
-        p_x, a_x, s_x, d1, d2, d3, b2, b3 = b[0]
-        p_prev, a_prev = b[1][0], b[1][1]
-        p_w, p_2w = b[2][0], b[3][0]
-        z = (pow(x, steps, P) - 1) % P
-        k_x, f0, f1, f2 = k_at[i], f0_at[i], f1_at[i], f2_at[i]
-        assert f0 * (p_x - f1 * p_prev - k_x * s_x) % P == z * d1 % P, "Q1 = Z * D1"
-        assert f2 * (p_2w - p_x * p_w) % P == z * d2 % P, "Q2 = Z * D2"
-        nmr = (r[0] + r[1] * ext_idx[pos] + r[2] * s_x) % P
-        dnm = (r[0] + r[1] * ext_pidx[pos] + r[2] * s_x) % P
-        assert (a_x * dnm - a_prev * nmr) % P == z * d3 % P, "Q3 = Z * D3"
         zb2 = 1
         for (_, w) in public_first_indices:
             zb2 = zb2 * (x - xs[w * skips]) % P
-        assert (s_x - eval_poly_at(interp2, x)) % P == zb2 * b2 % P, "S - I2 = Zb2 * B2"
-        assert (a_x - eval_poly_at(interp3, x)) % P == (x - x_last) * b3 % P, "A - I3 = Zb3 * B3"
-        xst = pow(x, steps, P)
-        l_x = fe(l_leaves[i])
-        want = (kk[0] * d1 + kk[1] * d2 + kk[2] * d3 + kk[3] * p_x + kk[4] * p_x * xst + kk[5] * b2
-                + kk[6] * b2 * xst + kk[7] * b3 + kk[8] * b3 * xst + kk[9] * a_x + kk[10] * s_x) % P
-        assert l_x == want, "linear combination"
+        for _, what, lhs, rhs in spot_equalities(main_leaves[i * 4:i * 4 + 4], l_leaves[i], pow(x, steps, P), k_at[i],
+                                                 f0_at[i], f1_at[i], f2_at[i], ext_idx[pos], ext_pidx[pos], r, kk,
+                                                 zb2, eval_poly_at(interp2, x), (x - x_last) % P,
+                                                 eval_poly_at(interp3, x)):
+            assert lhs == rhs, what
     return True

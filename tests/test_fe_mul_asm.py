@@ -2,7 +2,9 @@
 stark-pure-rust_amd/csrc/fe_mul_asm.inc) emulated instruction by instruction with exact
 integers for one lane: v_mad_u64_u32 / v_addc_co_u32 / v_sub(b)_co_u32 carry semantics, the
 alternating accumulator pairs, the column shifts and the Shoup product's rare-correction branch.
-  * Montgomery (single and the interleaved dual form): a*b*2^-256 mod p in [0, 2p) for a < 4p, b < p;
+  * Montgomery (single and the interleaved dual form): a*b*2^-256 mod p in [0, 2p) for any a < 2^256, b < p
+    (a < 4p + 2^224 is the NTT passes' lazy range; the rest is the verifier's, which multiplies 32 bytes as
+    they come by R^2 mod p);
   * Shoup: a*w mod p in [0, 2p) for any a < 2^256, including inputs built to make the truncated
     quotient one short (the flagged correction path)."""
 import os
@@ -134,13 +136,25 @@ def _mont_cases():
         [(rnd.randrange(4 * P, top + 1), rnd.randrange(P)) for _ in range(200)]
 
 
+def _mont_wide_cases():
+    """a in [4p + 2^224, 2^256): what csrc/verify_batch.hip's arena_mont and its I2 matrix kernel hand the product,
+    a leaf's or a public wire's 32 bytes as they are, against b = R^2 mod p (arena_mont's) and any b < p."""
+    rnd = random.Random(13)
+    lo, r2 = 4 * P + (1 << 224), R256 * R256 % P
+    assert 4 * P < lo < 5 * P - 1 < R256
+    edges = [R256 - 1, 5 * P - 1, 5 * P, lo]
+    cases = [(a, b) for a in edges for b in (r2, P - 1, 1, 0)]
+    cases += [(rnd.randrange(lo, R256), r2) for _ in range(700)]
+    return cases + [(rnd.randrange(lo, R256), rnd.randrange(P)) for _ in range(700)]
+
+
 def test_generated_montgomery_product():
     assert PINV == 0xEFFFFFFF  # STARK_PINV32 in fp_dev.h
     r = [f"%{i}" for i in range(8)]
     ops = G.stream(r, [f"%{9 + i}" for i in range(8)], [f"%{17 + i}" for i in range(8)],
                    [f"%{25 + i}" for i in range(8)], "%33", "%8", [(0, 1), (2, 3)])
     rinv = pow(R256, -1, P)
-    for a, b in _mont_cases():
+    for a, b in _mont_cases() + _mont_wide_cases():
         out = _out(_emulate(ops, _mont_regs(a, b, 9, 17, 25, "%33")), 0)
         assert out < 2 * P
         assert out % P == a * b * rinv % P
@@ -156,8 +170,11 @@ def test_generated_dual_product():
                   [(4, 5), (6, 7)])
     ops = [x for pr in zip(sa, sb) for x in pr]
     rinv = pow(R256, -1, P)
-    cases = _mont_cases()
-    for (a, b), (c, d) in zip(cases[:700], cases[700:1400]):
+    cases, wide = _mont_cases(), _mont_wide_cases()
+    half = len(wide) // 2
+    pairs = list(zip(cases[:700], cases[700:1400])) + list(zip(wide[:half], wide[half:2 * half]))
+    pairs += list(zip(wide[:300], cases[:300])) + list(zip(cases[300:600], wide[300:600]))  # wide beside narrow
+    for (a, b), (c, d) in pairs:
         regs = _mont_regs(a, b, 18, 26, 50, "%58")
         regs.update(_mont_regs(c, d, 34, 42))
         R = _emulate(ops, regs)
