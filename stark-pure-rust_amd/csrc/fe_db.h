@@ -39,7 +39,7 @@ __device__ __forceinline__ uint32_t db_n(int j) {
 }
 
 // 2^232 / p and 2^235 / p (nearest doubles) and the quotient margin 2^-12
-// (tests/test_fe_db.py checks every constant).
+// (tests/test_fe_db.py checks every constant; tests/test_gpu_fe_ops.py runs the compiled product next to the margin).
 #define STARK_DB_C8 3.153175148504101e-07
 #define STARK_DB_C7 2.5225401188032808e-06
 #define STARK_DB_MARGIN 2.44140625e-4

@@ -163,7 +163,8 @@ __device__ __forceinline__ fe fe_sub(const fe& a, const fe& b) {
 
 // Montgomery product, canonical result: any a < 2^256 with b < p (a b < 2^256 p, so the lazy product is below
 // 2p).  The batched verifier relies on the whole range: it multiplies a leaf's or a public wire's 32 bytes as
-// they are by R^2 mod p (verify_batch.hip arena_mont); tests/test_fe_mul_asm.py emulates the stream up to 2^256 - 1.
+// they are by R^2 mod p (verify_batch.hip arena_mont); tests/test_fe_mul_asm.py emulates the stream up to 2^256 - 1,
+// and tests/test_gpu_fe_ops.py runs this and every other primitive of this header on the GPU on directed operands.
 __device__ __forceinline__ fe fe_mul(const fe& a, const fe& b) {
   fe r = fe_mul_lazy(a, b);
   fe_reduce_once(r);

@@ -1158,6 +1158,133 @@ extern "C" int stark_test_ntt_plan(stark_ctx* ctx, uint64_t* d_data, uint32_t lo
                          nullptr, plan, policy, used);
 }
 
+// Test hook (not part of the ABI either): one field primitive of fp_dev.h / fe_mul_asm.inc / fe_db.h or one
+// lazy-range helper of this file per launch, one thread per record, so tests/test_gpu_fe_ops.py places
+// directed operands lane by lane (record i runs in lane i % 64 of wave i / 64).
+namespace stark {
+
+enum : uint32_t {
+  kFeAdd = 0, kFeAddRaw, kFeSub, kFeReduceOnce, kFeCsub2p, kFeBflyLazy, kFeBflyLazyReduced, kFeReduceLazy, kFeMul,
+  kFeMulLazy, kFeMulLazy2, kFeMulShoup, kFeMulDb, kFeMulDbUniform, kSub2p, kCsub2pTop, kBflyFast, kBflySlow,
+  kCsub2pTFast, kCsub2pTSlow, kReduceFullFast, kReduceFullSlow, kFeIsZero, kFeOpCount
+};
+// 32-byte elements read and written per record (fe_mul_db: a, then the 72-word table as nine elements).
+__host__ __device__ constexpr uint32_t fe_op_in(uint32_t op) {
+  return op == kFeMulDb || op == kFeMulDbUniform ? 10
+         : op == kFeMulLazy2                    ? 4
+         : op == kFeMulShoup                    ? 3
+         : op == kFeAdd || op == kFeAddRaw || op == kFeSub || op == kFeBflyLazy || op == kFeBflyLazyReduced ||
+                 op == kFeMul || op == kFeMulLazy || op == kBflyFast || op == kBflySlow
+             ? 2
+             : 1;
+}
+__host__ __device__ constexpr uint32_t fe_op_out(uint32_t op) {
+  return op == kFeBflyLazy || op == kFeBflyLazyReduced || op == kFeMulLazy2 || op == kBflyFast || op == kBflySlow ? 2
+                                                                                                                  : 1;
+}
+
+// W: the digit-basis table fe_mul_db reads (per lane, or the wave's first record's for kFeMulDbUniform).
+template <uint32_t OP>
+__device__ __forceinline__ void fe_op_apply(const fe* x, fe* y, const uint32_t* W) {
+  if constexpr (OP == kFeAdd) y[0] = fe_add(x[0], x[1]);
+  if constexpr (OP == kFeAddRaw) y[0] = fe_add_raw(x[0], x[1]);
+  if constexpr (OP == kFeSub) y[0] = fe_sub(x[0], x[1]);
+  if constexpr (OP == kFeMul) y[0] = fe_mul(x[0], x[1]);
+  if constexpr (OP == kFeMulLazy) y[0] = fe_mul_lazy(x[0], x[1]);
+  if constexpr (OP == kFeMulLazy2) fe_mul_lazy2(y[0], y[1], x[0], x[1], x[2], x[3]);
+  if constexpr (OP == kFeMulShoup) y[0] = fe_mul_shoup(x[0], x[1], x[2]);
+  if constexpr (OP == kFeMulDb || OP == kFeMulDbUniform) y[0] = fe_mul_db(x[0], W);
+  if constexpr (OP == kFeBflyLazy || OP == kFeBflyLazyReduced || OP == kBflyFast || OP == kBflySlow) {
+    y[0] = x[0];
+    if constexpr (OP == kFeBflyLazy) fe_bfly_lazy(y[0], y[1], x[1]);
+    if constexpr (OP == kFeBflyLazyReduced) fe_bfly_lazy_reduced(y[0], y[1], x[1]);
+    if constexpr (OP == kBflyFast) bfly<true>(y[0], y[1], x[1]);
+    if constexpr (OP == kBflySlow) bfly<false>(y[0], y[1], x[1]);
+  }
+  if constexpr (OP == kFeReduceOnce || OP == kFeCsub2p || OP == kFeReduceLazy || OP == kSub2p || OP == kCsub2pTop ||
+                OP == kCsub2pTFast || OP == kCsub2pTSlow || OP == kReduceFullFast || OP == kReduceFullSlow) {
+    y[0] = x[0];
+    if constexpr (OP == kFeReduceOnce) fe_reduce_once(y[0]);
+    if constexpr (OP == kFeCsub2p) fe_csub2p(y[0]);
+    if constexpr (OP == kFeReduceLazy) fe_reduce_lazy(y[0]);
+    if constexpr (OP == kSub2p) sub2p(y[0]);
+    if constexpr (OP == kCsub2pTop) csub2p_top(y[0]);
+    if constexpr (OP == kCsub2pTFast) csub2p_t<true>(y[0]);
+    if constexpr (OP == kCsub2pTSlow) csub2p_t<false>(y[0]);
+    if constexpr (OP == kReduceFullFast) reduce_full<true>(y[0]);
+    if constexpr (OP == kReduceFullSlow) reduce_full<false>(y[0]);
+  }
+  if constexpr (OP == kFeIsZero) {
+    y[0] = fe_zero();
+    y[0].w[0] = fe_is_zero(x[0]) ? 1u : 0u;
+  }
+}
+
+// odd_only: the primitive runs on odd lanes only, inside a divergent branch (a partial exec); even lanes
+// copy the record's first input element to every output element.
+template <uint32_t OP>
+__global__ __launch_bounds__(256) void fe_op_kernel(const fe* __restrict__ in, fe* __restrict__ out, uint32_t n,
+                                                    uint32_t odd_only) {
+  constexpr uint32_t NI = fe_op_in(OP), NO = fe_op_out(OP);
+  constexpr uint32_t NX = NI == 10 ? 1 : NI;  // (the table stays in memory)
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  fe x[NX], y[NO];
+#pragma unroll
+  for (uint32_t k = 0; k < NX; ++k) x[k] = fe_load(in + (size_t)i * NI + k);
+  // The wave's first record is below n whenever this lane's is; uniform, so the table may come through SGPRs.
+  const uint32_t rec = OP == kFeMulDbUniform ? __builtin_amdgcn_readfirstlane(i & ~63u) : i;
+  const uint32_t* W = reinterpret_cast<const uint32_t*>(in + (size_t)rec * NI + 1);
+  if (!odd_only || (threadIdx.x & 1)) {
+    fe_op_apply<OP>(x, y, W);
+  } else {
+    // The copy is loaded again, through a pointer the compiler cannot match with the load of x[0].  With
+    // y[k] = x[0] here the outputs and the first operand share one register tuple, and hipcc then put two
+    // early-clobber outputs of fe_bfly_lazy_reduced (after fe_csub2p) on the registers of its own x inputs:
+    // y came out as x + (x + t) + 2p - t in two words ("Field primitives").
+    const fe* again = in;
+    asm volatile("" : "+s"(again));
+    const fe c = fe_load(again + (size_t)i * NI);
+#pragma unroll
+    for (uint32_t k = 0; k < NO; ++k) y[k] = c;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < NO; ++k) fe_store(out + (size_t)i * NO + k, y[k]);
+}
+
+template <uint32_t OP>
+static void fe_op_launch(const fe* in, fe* out, uint32_t n, uint32_t odd_only, hipStream_t stream) {
+  hipLaunchKernelGGL(fe_op_kernel<OP>, dim3((n + 255) / 256), dim3(256), 0, stream, in, out, n, odd_only);
+}
+
+}  // namespace stark
+
+extern "C" int stark_test_fe_op(stark_ctx* ctx, uint32_t op, const uint64_t* d_in, uint64_t* d_out, size_t n_records,
+                                uint32_t lane_mask_mode, void* stream) {
+  using namespace stark;
+  if (!ctx || !d_in || !d_out || op >= kFeOpCount || n_records > ((size_t)1 << 20) || lane_mask_mode > 1)
+    return STARK_ERR_BAD_ARG;
+  if (n_records == 0) return STARK_OK;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const fe* in = (const fe*)d_in;
+  fe* out = (fe*)d_out;
+  const uint32_t n = (uint32_t)n_records;
+  hipStream_t s = pick_stream(ctx, stream);
+  switch (op) {
+#define STARK_FE_OP(K) case K: fe_op_launch<K>(in, out, n, lane_mask_mode, s); break;
+    STARK_FE_OP(kFeAdd) STARK_FE_OP(kFeAddRaw) STARK_FE_OP(kFeSub) STARK_FE_OP(kFeReduceOnce) STARK_FE_OP(kFeCsub2p)
+    STARK_FE_OP(kFeBflyLazy) STARK_FE_OP(kFeBflyLazyReduced) STARK_FE_OP(kFeReduceLazy) STARK_FE_OP(kFeMul)
+    STARK_FE_OP(kFeMulLazy) STARK_FE_OP(kFeMulLazy2) STARK_FE_OP(kFeMulShoup) STARK_FE_OP(kFeMulDb)
+    STARK_FE_OP(kFeMulDbUniform) STARK_FE_OP(kSub2p) STARK_FE_OP(kCsub2pTop) STARK_FE_OP(kBflyFast)
+    STARK_FE_OP(kBflySlow) STARK_FE_OP(kCsub2pTFast) STARK_FE_OP(kCsub2pTSlow) STARK_FE_OP(kReduceFullFast)
+    STARK_FE_OP(kReduceFullSlow) STARK_FE_OP(kFeIsZero)
+#undef STARK_FE_OP
+    default: return STARK_ERR_BAD_ARG;
+  }
+  STARK_HIP(ctx, hipGetLastError());
+  return STARK_OK;
+}
+
 namespace stark {
 
 uint32_t ntt_first_log_r(uint32_t log_n) { return log_n < 2 ? log_n : plan_passes(log_n).log_r[0]; }

@@ -3,8 +3,10 @@
 `tools/db_check.py:db_emulate` restates fe_mul_db step by step with exact integers and IEEE doubles;
 here it is run on random and edge inputs in the NTT's lazy range [0, 4p + 2^224), on inputs whose quotient
 estimate sits next to the margin, and the header's constants are checked against their definitions.
-The GPU side is exercised bit-exactly by every NTT parity test (tests/test_gpu_ntt.py,
-tests/test_gpu_large.py) and by tools/microbench/db_rate.hip (65,536 products vs Python).
+On the GPU the compiled fe_mul_db is given the same edge and next-to-the-margin inputs, table per lane and
+table through a wave-uniform pointer, and compared word for word with db_emulate (tests/test_gpu_fe_ops.py);
+every NTT parity test (tests/test_gpu_ntt.py, tests/test_gpu_large.py) exercises it on random data, and
+tools/microbench/db_rate.hip times it (65,536 products vs Python).
 """
 import os
 import random

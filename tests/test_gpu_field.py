@@ -64,6 +64,23 @@ def test_lde(ctx, oracle, log_steps, log_blowup):
     assert np.array_equal(ctx.lde(v, g1, log_blowup, g2), want)
 
 
+# (8, 8), (13, 3): sparse radix-2^8 first passes; (12, 2), (9, 5): sparse radix-2^7 ones (see test_lde)
+@pytest.mark.parametrize("log_steps,log_blowup", [(4, 3), (8, 8), (12, 2), (9, 5), (13, 3)])
+def test_lde_closed_form(ctx, log_steps, log_blowup):
+    """The LDE of a polynomial's evaluations is the same polynomial on the larger domain: a constant column
+    (every coefficient but the first is the canonical zero) and 3 + 5 X, in Python integers."""
+    log_prec = log_steps + log_blowup
+    g2 = O.root_of_unity(log_prec)
+    g1 = pow(g2, 1 << log_blowup, O.P)
+    for c0, c1 in ((O.P - 1, 0), (3, 5)):
+        xs, x = [], 1
+        for _ in range(1 << log_prec):
+            xs.append((c0 + c1 * x) % O.P)
+            x = x * g2 % O.P
+        v = O.to_limbs(xs[::1 << log_blowup])       # g1^i = g2^(i 2^log_blowup)
+        assert O.from_limbs(ctx.lde(v, g1, log_blowup, g2)) == xs, (c0, c1)
+
+
 def test_lde_dev_batch(ctx, oracle):
     log_steps, log_blowup, batch = 11, 3, 3
     log_prec = log_steps + log_blowup

@@ -9,6 +9,11 @@ The default plans launch only some of these; the rest are reached through the li
     table, and once on a context whose cache cap is 0, where it takes the two-level form.
 Forward and inverse are compared bit for bit with the oracle; the 2^17 plans share one expected output
 per direction.
+
+The same plans also transform structured inputs whose outputs are known in closed form (Python integers, no
+oracle): the constant p - 1, a delta of p - 1 at 1 and at n - 1, and the pure tones (p - 1) w^(-m i) for
+m = 1, n / 2 + 1, n - 1.  A tone's butterflies meet X' = T (mod p) at every stage, so the passes' lazy values
+are exactly p, 2p and 3p and the last reduction takes exactly p: values random data never produces.
 """
 import ctypes
 import functools
@@ -39,9 +44,10 @@ def _limbs(x):
     return (ctypes.c_uint64 * 4)(*[(x >> (64 * k)) & (2**64 - 1) for k in range(4)])
 
 
-def _plan_ntt(c, log_n, inverse, plan):
+def _plan_ntt(c, log_n, inverse, plan, x=None):
     assert sum(plan) == log_n
-    x = _input(log_n)
+    if x is None:
+        x = _input(log_n)
     used = ctypes.c_uint32(0xFFFFFFFF)
     d = c.alloc(x.nbytes)
     try:
@@ -75,6 +81,53 @@ def _want(log_n, inverse):
     return out
 
 
+STRUCTURED = ("const", "delta_1", "delta_last", "tone_1", "tone_half_1", "tone_last")
+
+
+def _to_limbs(vals):
+    a = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
+    a.setflags(write=False)
+    return a
+
+
+def _powers(c, g, n):
+    """c g^k, k < n."""
+    out = [c] * n
+    for k in range(1, n):
+        out[k] = out[k - 1] * g % O.P
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _structured(log_n, kind):
+    """(input, forward transform, inverse transform) in closed form: out[k] = sum_j x[j] w^(j k) forward,
+    n^-1 sum_j x[j] w^(-j k) inverse."""
+    n, w, v = 1 << log_n, O.root_of_unity(log_n), O.P - 1
+    n_inv = pow(n, -1, O.P)
+    fwd, inv = [0] * n, [0] * n
+    if kind == "const":
+        x = [v] * n
+        fwd[0], inv[0] = n * v % O.P, v
+    elif kind.startswith("delta"):
+        j = 1 if kind == "delta_1" else n - 1
+        x = [0] * n
+        x[j] = v
+        fwd, inv = _powers(v, pow(w, j, O.P), n), _powers(v * n_inv % O.P, pow(w, -j, O.P), n)
+    else:
+        m = {"tone_1": 1, "tone_half_1": n // 2 + 1, "tone_last": n - 1}[kind]
+        x = _powers(v, pow(w, -m, O.P), n)
+        fwd[m], inv[n - m] = n * v % O.P, v
+    return _to_limbs(x), _to_limbs(fwd), _to_limbs(inv)
+
+
+def _check_structured(c, log_n, plan):
+    for kind in STRUCTURED:
+        x, fwd, inv = _structured(log_n, kind)
+        for inverse, want in ((False, fwd), (True, inv)):
+            got = _plan_ntt(c, log_n, inverse, plan, x)
+            assert np.array_equal(got, want), (plan, kind, inverse, np.flatnonzero((got != want).any(axis=1))[:8])
+
+
 @pytest.fixture(scope="module")
 def ctx_nocache():
     c = S.Context(0)
@@ -91,6 +144,23 @@ def test_small_pair(ctx, r, first):
     for inverse in (False, True):
         got = _plan_ntt(ctx, log_n, inverse, plan)
         assert np.array_equal(got, _want(log_n, inverse)), (plan, inverse)
+
+
+@pytest.mark.parametrize("first", [False, True], ids=["last", "first"])
+@pytest.mark.parametrize("r", RADICES)
+def test_small_pair_structured(ctx, r, first):
+    _check_structured(ctx, 4 + r, (r, 4) if first else (4, r))
+
+
+@pytest.mark.parametrize("r", RADICES)
+def test_2_17_full_table_structured(ctx, r):
+    _check_structured(ctx, 17, PREFIX_2_17[r] + (r,))
+
+
+@pytest.mark.parametrize("r", RADICES)
+def test_2_17_two_level_structured(ctx_nocache, r):
+    _check_structured(ctx_nocache, 17, PREFIX_2_17[r] + (r,))
+    assert ctx_nocache.memory()["cached"] == 0
 
 
 @pytest.mark.parametrize("r", RADICES)
