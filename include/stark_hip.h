@@ -45,8 +45,9 @@ extern "C" {
  * 9: stark_verify_r1cs_circuit_batch, stark_ctx_set_verify_batch_limit, STARK_VERIFY_FAIL_*.
  * 10: stark_verify_r1cs_circuit_batch_proofs, stark_r1cs_proof_from_parts,
  *     stark_ctx_set_verify_batch_transcript.
- * 11: stark_interp_plan_*, stark_lagrange_interp_batch. */
-#define STARK_ABI_VERSION 11u
+ * 11: stark_interp_plan_*, stark_lagrange_interp_batch.
+ * 12: stark_fri_proof_from_parts, stark_verify_low_degree_batch, stark_ctx_set_verify_batch_last. */
+#define STARK_ABI_VERSION 12u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -132,6 +133,13 @@ stark_status stark_ctx_set_verify_batch_limit(stark_ctx* ctx, size_t bytes);
  * stark_verify_r1cs_circuit_batch and stark_verify_r1cs_circuit_batch_proofs and changes no status and no
  * reason.  Any other mode is STARK_ERR_BAD_ARG. */
 stark_status stark_ctx_set_verify_batch_transcript(stark_ctx* ctx, uint32_t mode);
+/* Who checks the FriProof::Last elements (fri.rs:346-403) of stark_verify_low_degree_batch's chain proofs (no
+ * reference counterpart): 1 the host workers, one proof per worker beside the device chain; 2 the device -- the
+ * tree over the raw Last values against the root the layers before it leave, and the degree of the values through
+ * one check matrix that every proof of the call shares; 0 the library's default (the host).  It
+ * changes no status and no reason, and it does not apply to stark_verify_r1cs_circuit_batch(_proofs), whose Last
+ * layers stay on the host.  Any other mode is STARK_ERR_BAD_ARG. */
+stark_status stark_ctx_set_verify_batch_last(stark_ctx* ctx, uint32_t mode);
 
 /* ---- NTT (packages/fri/src/fft.rs) --------------------------------------- */
 /* best_fft<T>(coefficients: Vec<T>, root_of_unity: &T, log_order_of_root: u32) -> Vec<T>
@@ -613,6 +621,14 @@ stark_status stark_r1cs_proof_from_parts(const uint8_t m_root[32], const uint8_t
                                          const stark_branches* linear_comb_branches,
                                          const stark_fri_layer_parts* layers, size_t n_layers,
                                          const uint8_t* last_values, size_t n_last, stark_r1cs_proof** out);
+/* A Vec<FriProof<BlakeDigest>> handle (fri.rs:16-26) over copies of its parts (host only, no context): the Middle
+ * layers, then one Last of n_last 32-byte values -- stark_r1cs_proof_from_parts' counterpart for a standalone FRI
+ * proof, what a caller that received a proof passes to stark_verify_low_degree_batch.  The handle works with every
+ * stark_fri_proof_* accessor and with stark_fri_proof_json, and is freed with stark_fri_proof_free.
+ * STARK_ERR_BAD_ARG (*out NULL): a null `out`, a null array whose count is not zero, a null root2, a leaf_len of 0,
+ * a size product that overflows.  Nothing else about the parts is judged here: the verifier judges them. */
+stark_status stark_fri_proof_from_parts(const stark_fri_layer_parts* layers, size_t n_layers,
+                                        const uint8_t* last_values, size_t n_last, stark_fri_proof** out);
 /* mk_r1cs_proof (prove.rs:14-264) for rank `rank` of `world`: the trace set-up,
  * accumulator tree and transcript r on every rank, then this rank's residue
  * class of the precision domain: coset LDEs (no exchange: degree < steps <=
@@ -744,6 +760,34 @@ stark_status stark_verify_low_degree_proof(const uint8_t merkle_root[32], const 
                                            const stark_fri_layer_parts* layers, size_t n_layers,
                                            const uint8_t* const* last_values, const size_t* last_lens,
                                            size_t n_last, size_t max_deg_plus_1, uint32_t exclude_multiples_of);
+/* verify_low_degree_proof (fri.rs:226-404) for `batch` proofs of one (root of unity, degree bound, exclusion):
+ * statuses[b] is what stark_verify_low_degree_proof returns for merkle_roots + 32 b and the parts of proofs[b],
+ * always -- that call's STARK_ERR_BAD_ARG cases included (a root that is not of 2-power order, an empty proof, a
+ * Last in the middle, no Last).  The reference has no batched verifier: a proof whose structure is exactly what
+ * prove_low_degree (fri.rs:46-224) makes of n = the root's order and max_deg_plus_1 -- L Middle layers, L the
+ * divisions by 4 while the bound exceeds 16; 40 column and 160 polynomial openings per layer with 32-byte leaves
+ * and one node per tree level; a Last of n / 4^L values -- is checked on the GPU: every Merkle path
+ * (Proof::validate, merkle_tree.rs:25-43) and every row (fri.rs:318-345) of a chunk by one launch each, and the
+ * Last elements (fri.rs:346-403) by the tree over their raw values and one check matrix shared by the call
+ * (stark_ctx_set_verify_batch_last; mode 1 leaves them to the host workers).  Every other proof, and every proof
+ * of a parameter set the chain cannot take (the sampler's bounds, fri/src/utils.rs:88 and :101; n > 2^28; more
+ * than 16 layers; a check matrix above a quarter of the staging cap), goes through the single-proof verifier.
+ * A handle is untrusted input: every index is derived from the roots as given, the prover's own index vectors are
+ * never read, and nothing a handle supplies is a length or an offset on the device.
+ * Whole-call errors (STARK_ERR_BAD_ARG, nothing read or written, no device call): a null ctx, merkle_roots,
+ * root_of_unity or proofs, batch > 65535.  batch == 0 is then STARK_OK.  A null proofs[b] is that entry's
+ * STARK_ERR_BAD_ARG.  With statuses != NULL the call returns STARK_OK (or a device error); with statuses == NULL
+ * it returns the first status in batch order that is not STARK_OK.  One proof's failure changes no other proof's
+ * status.  reasons (optional): 0 where statuses[b] is STARK_OK; for a proof of the chain the OR of
+ * STARK_VERIFY_FAIL_FRI_PATHS, _FRI_ROWS and _FRI_LAST, each evaluated independently of the others from the proof
+ * as given (rows on the leaves' values whether or not their paths hold; _FRI_LAST for everything the Last
+ * element's check can refuse); STARK_VERIFY_FAIL_SINGLE alone for every other entry that is not STARK_OK.
+ * Chunks follow stark_ctx_set_verify_batch_limit; the staging buffers are reused across calls and counted in
+ * stark_ctx_memory's resident_bytes. */
+stark_status stark_verify_low_degree_batch(stark_ctx* ctx, const uint8_t* merkle_roots /* batch x 32 */,
+                                           const uint64_t root_of_unity[4], const stark_fri_proof* const* proofs,
+                                           uint32_t batch, size_t max_deg_plus_1, uint32_t exclude_multiples_of,
+                                           stark_status* statuses, uint32_t* reasons);
 /* verify_with_witness (run.rs:454-526) on a prepared circuit; public_wires = n_public
  * 32-byte little-endian integers (n_public >= 1 + n_public_inputs + n_public_outputs). */
 stark_status stark_verify_r1cs_circuit(stark_ctx* ctx, const stark_r1cs_circuit* circuit,

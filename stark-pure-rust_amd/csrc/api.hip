@@ -325,6 +325,8 @@ void stark_ctx_destroy(stark_ctx* ctx) {
     stark_merkle_forest_free(f);
     f = nullptr;
   }
+  stark_merkle_forest_free(ctx->verify_forest);
+  ctx->verify_forest = nullptr;
   for (void* p : ctx->pinned)
     if (p) hipHostFree(p);
   for (auto& kv : ctx->ext_idx)
@@ -390,13 +392,15 @@ stark_status stark_ctx_set_verify_batch_limit(stark_ctx* ctx, size_t bytes) {
   ctx->verify_batch_limit = bytes;
   // What a batch left behind goes when it is above the new cap (the next batch allocates its chunk's size).
   const size_t cap = bytes ? bytes : kDefaultVerifyBatchLimit;
-  const size_t held = std::max(ctx->verify_batch.ptr ? ctx->verify_batch.bytes : 0, ctx->pinned_bytes[7]);
+  const size_t held = std::max(ctx->verify_batch.ptr ? ctx->verify_batch.bytes : 0, ctx->pinned_bytes[7]) +
+                      forest_device_bytes(ctx->verify_forest);
   if (held > cap) {
     STARK_HIP(ctx, hipDeviceSynchronize());  // (a kernel or copy of any stream may still use them)
     if (ctx->verify_batch.ptr) hipFree(ctx->verify_batch.ptr);
     ctx->verify_batch.ptr = nullptr;
     ctx->verify_batch.bytes = 0;
     ctx->verify_batch.last = nullptr;
+    forest_release(ctx->verify_forest);
     if (ctx->pinned[7]) hipHostFree(ctx->pinned[7]);
     ctx->pinned[7] = nullptr;
     ctx->pinned_bytes[7] = 0;
@@ -407,6 +411,12 @@ stark_status stark_ctx_set_verify_batch_limit(stark_ctx* ctx, size_t bytes) {
 stark_status stark_ctx_set_verify_batch_transcript(stark_ctx* ctx, uint32_t mode) {
   if (!ctx || mode > 2) return STARK_ERR_BAD_ARG;
   ctx->verify_batch_transcript = mode;
+  return STARK_OK;
+}
+
+stark_status stark_ctx_set_verify_batch_last(stark_ctx* ctx, uint32_t mode) {
+  if (!ctx || mode > 2) return STARK_ERR_BAD_ARG;
+  ctx->verify_batch_last = mode;
   return STARK_OK;
 }
 
@@ -428,6 +438,7 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   total += ctx->pinned_bytes[5];
   // stark_verify_r1cs_circuit_batch's staging (its device image is among the buffers above)
   total += ctx->pinned_bytes[7];
+  total += forest_device_bytes(ctx->verify_forest);  // stark_verify_low_degree_batch's wide Last elements
   // stark_prove_r1cs_circuit_batch's forests (its arena is among the buffers above)
   for (const stark_merkle_forest* f : ctx->r1cs_forests) total += forest_device_bytes(f);
   for (const InterpPlan* p : ctx->interp_plans) total += p->bytes;  // the interpolation plans alive on this context

@@ -1052,49 +1052,37 @@ stark_status stark_r1cs_proof_json_from_parts(const uint8_t m_root[32], const ui
   return STARK_OK;
 }
 
-// A handle over copies of the caller's parts.  Only what the copies need is judged here: the verifier judges
-// the rest (a handle is untrusted input to it).
-stark_status stark_r1cs_proof_from_parts(const uint8_t m_root[32], const uint8_t l_root[32], const uint8_t a_root[32],
-                                         const stark_branches* main_branches,
-                                         const stark_branches* linear_comb_branches,
-                                         const stark_fri_layer_parts* layers, size_t n_layers,
-                                         const uint8_t* last_values, size_t n_last, stark_r1cs_proof** out) {
-  if (!out) return STARK_ERR_BAD_ARG;
-  *out = nullptr;
-  if (!m_root || !l_root || !a_root || !main_branches || !linear_comb_branches) return STARK_ERR_BAD_ARG;
-  if ((n_layers && !layers) || (n_last && !last_values)) return STARK_ERR_BAD_ARG;
+}  // extern "C"
+
+namespace stark {
+namespace {
+// k x leaf_len and k x depth x 32 bytes of one set of openings, copied; false for a leaf_len of 0, a size product
+// that overflows or a null array whose size is not zero.
+bool take_branches(const stark_branches& B, std::vector<uint8_t>& leaves, std::vector<uint8_t>& nodes) {
+  size_t lb = 0, nb = 0;
+  if (B.leaf_len == 0 || __builtin_mul_overflow(B.k, B.leaf_len, &lb) || __builtin_mul_overflow(B.k, B.depth, &nb) ||
+      __builtin_mul_overflow(nb, (size_t)32, &nb))
+    return false;
+  if ((lb && !B.leaves) || (nb && !B.nodes)) return false;
+  leaves.assign(B.leaves, B.leaves + lb);
+  nodes.assign(B.nodes, B.nodes + nb);
+  return true;
+}
+// A Vec<FriProof> over copies of its parts: the Middle layers, then one Last of n_last 32-byte values.  Null where
+// the copies cannot be made (stark_fri_proof_from_parts' STARK_ERR_BAD_ARG cases but the null `out`).
+std::unique_ptr<stark_fri_proof> fri_from_parts(const stark_fri_layer_parts* layers, size_t n_layers,
+                                                const uint8_t* last_values, size_t n_last) {
+  if ((n_layers && !layers) || (n_last && !last_values)) return nullptr;
   size_t last_bytes = 0;
-  if (__builtin_mul_overflow(n_last, (size_t)32, &last_bytes)) return STARK_ERR_BAD_ARG;
-  // k x leaf_len and k x depth x 32 bytes of one set of openings, copied.
-  auto take = [](const stark_branches& B, std::vector<uint8_t>& leaves, std::vector<uint8_t>& nodes) {
-    size_t lb = 0, nb = 0;
-    if (B.leaf_len == 0 || __builtin_mul_overflow(B.k, B.leaf_len, &lb) || __builtin_mul_overflow(B.k, B.depth, &nb) ||
-        __builtin_mul_overflow(nb, (size_t)32, &nb))
-      return false;
-    if ((lb && !B.leaves) || (nb && !B.nodes)) return false;
-    leaves.assign(B.leaves, B.leaves + lb);
-    nodes.assign(B.nodes, B.nodes + nb);
-    return true;
-  };
-  std::unique_ptr<stark_r1cs_proof> p(new stark_r1cs_proof);
-  memcpy(p->m_root, m_root, 32);
-  memcpy(p->l_root, l_root, 32);
-  memcpy(p->a_root, a_root, 32);
-  p->json_lazy = true;
-  if (!take(*main_branches, p->m_leaves, p->m_nodes) || !take(*linear_comb_branches, p->l_leaves, p->l_nodes))
-    return STARK_ERR_BAD_ARG;
-  p->m_leaf_len = main_branches->leaf_len;
-  p->l_leaf_len = linear_comb_branches->leaf_len;
-  p->depth = main_branches->depth;
-  p->l_depth = linear_comb_branches->depth;
+  if (__builtin_mul_overflow(n_last, (size_t)32, &last_bytes)) return nullptr;
   std::unique_ptr<stark_fri_proof> fri(new stark_fri_proof);
   for (size_t l = 0; l < n_layers; ++l) {
     const stark_fri_layer_parts& P = layers[l];
-    if (!P.root2) return STARK_ERR_BAD_ARG;
+    if (!P.root2) return nullptr;
     stark_fri_layer L;
     memcpy(L.root2, P.root2, 32);
-    if (!take(P.column, L.col_leaves, L.col_nodes) || !take(P.poly, L.poly_leaves, L.poly_nodes))
-      return STARK_ERR_BAD_ARG;
+    if (!take_branches(P.column, L.col_leaves, L.col_nodes) || !take_branches(P.poly, L.poly_leaves, L.poly_nodes))
+      return nullptr;
     L.col_idx.resize(P.column.k);  // (counts only: the prover's indices are unknown here and nothing reads them)
     L.poly_idx.resize(P.poly.k);
     L.col_leaf_len = P.column.leaf_len;
@@ -1108,6 +1096,48 @@ stark_status stark_r1cs_proof_from_parts(const uint8_t m_root[32], const uint8_t
   memset(last.root2, 0, 32);
   if (last_bytes) last.last_values.assign(last_values, last_values + last_bytes);
   fri->layers.push_back(std::move(last));
+  return fri;
+}
+}  // namespace
+}  // namespace stark
+
+extern "C" {
+
+// A Vec<FriProof> handle over copies of the caller's parts (host only).  Only what the copies need is judged here.
+stark_status stark_fri_proof_from_parts(const stark_fri_layer_parts* layers, size_t n_layers,
+                                        const uint8_t* last_values, size_t n_last, stark_fri_proof** out) {
+  if (!out) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  std::unique_ptr<stark_fri_proof> fri = fri_from_parts(layers, n_layers, last_values, n_last);
+  if (!fri) return STARK_ERR_BAD_ARG;
+  *out = fri.release();
+  return STARK_OK;
+}
+
+// A handle over copies of the caller's parts.  Only what the copies need is judged here: the verifier judges
+// the rest (a handle is untrusted input to it).
+stark_status stark_r1cs_proof_from_parts(const uint8_t m_root[32], const uint8_t l_root[32], const uint8_t a_root[32],
+                                         const stark_branches* main_branches,
+                                         const stark_branches* linear_comb_branches,
+                                         const stark_fri_layer_parts* layers, size_t n_layers,
+                                         const uint8_t* last_values, size_t n_last, stark_r1cs_proof** out) {
+  if (!out) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  if (!m_root || !l_root || !a_root || !main_branches || !linear_comb_branches) return STARK_ERR_BAD_ARG;
+  std::unique_ptr<stark_r1cs_proof> p(new stark_r1cs_proof);
+  memcpy(p->m_root, m_root, 32);
+  memcpy(p->l_root, l_root, 32);
+  memcpy(p->a_root, a_root, 32);
+  p->json_lazy = true;
+  if (!take_branches(*main_branches, p->m_leaves, p->m_nodes) ||
+      !take_branches(*linear_comb_branches, p->l_leaves, p->l_nodes))
+    return STARK_ERR_BAD_ARG;
+  p->m_leaf_len = main_branches->leaf_len;
+  p->l_leaf_len = linear_comb_branches->leaf_len;
+  p->depth = main_branches->depth;
+  p->l_depth = linear_comb_branches->depth;
+  std::unique_ptr<stark_fri_proof> fri = fri_from_parts(layers, n_layers, last_values, n_last);
+  if (!fri) return STARK_ERR_BAD_ARG;
   p->fri = fri.release();
   *out = p.release();
   return STARK_OK;

@@ -160,6 +160,12 @@ constexpr size_t kDefaultVerifyBatchLimit = (size_t)256 << 20;
 // Who derives the batched verifier's transcript by default: 1 the host, 2 the device
 // (stark_ctx_set_verify_batch_transcript).
 constexpr uint32_t kDefaultVerifyTranscript = 1;
+// Who checks the Last elements of stark_verify_low_degree_batch's chain proofs by default: 1 the host workers,
+// 2 the device (stark_ctx_set_verify_batch_last).  Measured (profiles/fri_verify_batch_ab.txt): the
+// device form costs some 0.075 ms more per call -- three more launches behind the chain, where the host workers
+// check the Last elements beside it -- which at 64 proofs is beyond three of the host form's spreads, and the two
+// tie from 256 proofs on: the host.
+constexpr uint32_t kDefaultVerifyLast = 1;
 
 }  // namespace stark
 
@@ -207,6 +213,12 @@ struct stark_ctx {
   // Who derives a chain proof's indices, challenges and records (stark_ctx_set_verify_batch_transcript): 0 the
   // default (stark::kDefaultVerifyTranscript), 1 the host, 2 the device.
   uint32_t verify_batch_transcript = 0;
+  // stark_verify_low_degree_batch (verify_batch.hip) stages its chunks in verify_batch and pinned slot 7 too.  Who
+  // checks its Last elements (stark_ctx_set_verify_batch_last): 0 the default (stark::kDefaultVerifyLast), 1 the
+  // host, 2 the device; verify_forest: the trees over Last elements too wide for one workgroup (created on first
+  // use, reused across calls, released with the staging when the cap is lowered below what they hold).
+  uint32_t verify_batch_last = 0;
+  stark_merkle_forest* verify_forest = nullptr;
   // pinned host scratch (ctx_pinned)
   void* pinned[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t pinned_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};

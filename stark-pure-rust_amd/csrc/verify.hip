@@ -689,6 +689,11 @@ uint32_t log2_ceil_ref(size_t v) {  // log2_ceil (r1cs-stark/src/utils.rs:14-23)
 
 }  // namespace
 
+stark_status verify_fri_single(const uint8_t merkle_root[32], const HostFp& root, const std::vector<FriIn>& proof,
+                               size_t max_deg_plus_1, uint32_t excl) {
+  return verify_fri(merkle_root, root, proof, max_deg_plus_1, excl);
+}
+
 stark_status fri_last_check(const FriIn& last, const uint8_t m_root[32], const HostFp& root, size_t max_deg_plus_1,
                             uint32_t excl) {
   const FieldHost& F = FieldHost::get();

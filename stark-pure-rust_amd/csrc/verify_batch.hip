@@ -20,6 +20,9 @@
 // device's transcript (the host then uploads openings only); verify_interp2_batch_kernel forms every chain proof's
 // I2 from the Lagrange basis of the circuit's boundary points where that matrix is small enough; from the
 // verification threshold on, one application of the circuit's interpolation plan (poly.hip) forms them instead.
+//
+// The file's second part is the same chain for standalone FRI proofs (stark_verify_low_degree_batch): the path and
+// row kernels above on stark_fri_proof handles, and the Last element's kernels.
 #include <string.h>
 
 #include <algorithm>
@@ -516,18 +519,12 @@ bool view_branches(const std::vector<uint8_t>& leaves, size_t leaf_len, const st
   }
   return true;
 }
-bool view_proof(const stark_r1cs_proof& h, ProofIn& pr) {
-  if (!h.fri) return false;
-  memcpy(pr.m_root, h.m_root, 32);
-  memcpy(pr.l_root, h.l_root, 32);
-  memcpy(pr.a_root, h.a_root, 32);
-  if (!view_branches(h.m_leaves, h.m_leaf_len, h.m_nodes, h.depth_of(0), pr.main) ||
-      !view_branches(h.l_leaves, h.l_leaf_len, h.l_nodes, h.depth_of(1), pr.lcomb))
-    return false;
-  pr.fri.resize(h.fri->layers.size());
-  for (size_t l = 0; l < pr.fri.size(); ++l) {
-    const stark_fri_layer& L = h.fri->layers[l];
-    FriIn& f = pr.fri[l];
+// A Vec<FriProof> handle's layers (the FRI part of a StarkProof handle, or a standalone proof's handle).
+bool view_fri(const stark_fri_proof& h, std::vector<FriIn>& out) {
+  out.resize(h.layers.size());
+  for (size_t l = 0; l < out.size(); ++l) {
+    const stark_fri_layer& L = h.layers[l];
+    FriIn& f = out[l];
     f.last = L.last;
     if (L.last) {
       for (size_t i = 0; i + 32 <= L.last_values.size(); i += 32)
@@ -540,6 +537,16 @@ bool view_proof(const stark_r1cs_proof& h, ProofIn& pr) {
       return false;
   }
   return true;
+}
+bool view_proof(const stark_r1cs_proof& h, ProofIn& pr) {
+  if (!h.fri) return false;
+  memcpy(pr.m_root, h.m_root, 32);
+  memcpy(pr.l_root, h.l_root, 32);
+  memcpy(pr.a_root, h.a_root, 32);
+  if (!view_branches(h.m_leaves, h.m_leaf_len, h.m_nodes, h.depth_of(0), pr.main) ||
+      !view_branches(h.l_leaves, h.l_leaf_len, h.l_nodes, h.depth_of(1), pr.lcomb))
+    return false;
+  return view_fri(*h.fri, pr.fri);
 }
 
 // One entry's proof as the caller gave it: serde_json text, or a handle.
@@ -1038,11 +1045,547 @@ static stark_status verify_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, 
   return STARK_OK;
 }
 
+// ---- standalone FRI proofs: stark_verify_low_degree_batch ----
+//
+// verify_low_degree_proof (fri.rs:226-404) for many stark_fri_proof handles of one (root of unity, degree bound,
+// exclusion).  The chain is the one above without a circuit: the host views each handle's vectors (view_fri),
+// screens its structure against what prove_low_degree makes of the parameters (fri_in_shape), samples each
+// layer's rows from the roots as given and packs the openings with the same PathRec / RowRec records; one upload,
+// verify_paths_batch_kernel, verify_fri_rows_batch_kernel, the Last element's kernels below, one download of the
+// ok bytes.  Every other proof goes to verify_fri_single, so each status is stark_verify_low_degree_proof's.
+//
+// A handle is untrusted input (stark_fri_proof_from_parts makes one of anything).  As above, nothing a handle
+// supplies is used as a length or an offset on the device: every offset in a record comes from the parameters'
+// shape (FriShape), every index from the sampler below its tree's size, and the Last kernels take the count of
+// values, the interpolation positions and the rest positions from the parameters alone.  A handle's bytes are only
+// ever hashed or multiplied.
+//
+// The Last element (fri.rs:346-403; fri_last_check): all proofs of a call share w = root^(4^L), n_last, the degree
+// bound m and the exclusion, hence the admissible positions: the first m are the interpolation points x_i, the
+// others the rest points x_r.  "The values at the rest points lie on the polynomial through the first m" is
+//   y_r = sum_i M[r][i] y_i,   M[r][i] = L_i(x_r) = w_i prod_(j != i) (x_r - x_j),   w_i = 1 / prod_(j != i) (x_i - x_j),
+// with one matrix for the whole call: verify_last_matrix_kernel forms it once (the m weights and points come from
+// the host: m <= 16 for a proof of the chain), verify_last_degree_batch_kernel applies it, one lane per (proof,
+// rest point).  The field arithmetic is exact, so the outcome is eval_poly(lagrange_interp(..)) == y_r's.
+
+namespace {
+
+// The k-th position that is no multiple of excl (excl >= 2), or k itself without an exclusion (fri.rs:377-385).
+__host__ __device__ inline uint64_t admissible_pos(uint64_t k, uint32_t excl) {
+  return excl ? k + 1 + k / (excl - 1) : k;
+}
+
+// What every proof of the call shares of its Last element.
+struct LastArgs {
+  uint32_t n_last, m, n_rest, excl;
+  uint32_t o_xi, o_mat;  // the m interpolation points (Montgomery images), the matrix [i][r] (m x n_rest)
+  fe w, r2m, one;        // the Last element's root of unity, R^2, 1
+};
+
+// The check matrix, one lane per (i, r): Mt[i n_rest + r] = w_i prod_(j != i) (x_r - x_j), x_r = w^pos(m + r)
+// (pos < n_last: the host counted the admissible positions).  A lane's i is uniform over a wave but at a row's end.
+__global__ __launch_bounds__(kThreads) void verify_last_matrix_kernel(uint8_t* arena, const fe* __restrict__ wi,
+                                                                       LastArgs A) {
+  const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
+  if (g >= A.m * A.n_rest) return;
+  const uint32_t i = g / A.n_rest, r = g % A.n_rest;
+  const fe* xi = reinterpret_cast<const fe*>(arena + A.o_xi);
+  const fe x = fe_pow(A.w, admissible_pos((uint64_t)A.m + r, A.excl), A.one);
+  fe acc = fe_load(wi + i);
+  for (uint32_t j = 0; j < A.m; ++j) {
+    const fe t = fe_mul(acc, fe_sub(x, fe_load(xi + j)));
+    if (j != i) acc = t;
+  }
+  fe_store(reinterpret_cast<fe*>(arena + A.o_mat) + g, acc);
+}
+
+// One lane per (proof, rest point): sum_i Mt[i][r] y_i against y_r on Montgomery images, the y's being
+// from_bytes_le of the raw 32 bytes (any value below 2^256: arena_mont).  Proof k's values are the n_last x 32 B
+// at o_last + 32 k n_last; a wave's lanes share the proof (but at a proof's end) and read the matrix side by side.
+__global__ __launch_bounds__(kThreads) void verify_last_degree_batch_kernel(const uint8_t* __restrict__ arena,
+                                                                             uint64_t o_last, uint32_t nb, LastArgs A,
+                                                                             uint8_t* __restrict__ ok) {
+  const uint64_t g = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (g >= (uint64_t)nb * A.n_rest) return;
+  const uint32_t k = (uint32_t)(g / A.n_rest), r = (uint32_t)(g % A.n_rest);
+  const uint8_t* vals = arena + o_last + (uint64_t)32 * k * A.n_last;
+  const fe* mt = reinterpret_cast<const fe*>(arena + A.o_mat);
+  auto y_at = [&](uint64_t pos) { return fe_mul(fe_load(reinterpret_cast<const fe*>(vals + 32 * pos)), A.r2m); };
+  fe acc = fe_zero();
+  for (uint32_t i = 0; i < A.m; ++i)
+    acc = fe_add(acc, fe_mul(fe_load(mt + (size_t)i * A.n_rest + r), y_at(admissible_pos(i, A.excl))));
+  ok[g] = fe_eq(acc, y_at(admissible_pos((uint64_t)A.m + r, A.excl)));
+}
+
+// The tree over a proof's raw Last values (fri.rs:367-372) against the root the layers before it leave, one
+// workgroup per proof through LDS: leaf digests, then one level per step, two pair hashes per lane at the widest.
+// Taken up to kLastLdsMax = 1,024 values (the common Lasts hold 32 or 64): that many digests are 32 KB of LDS, and
+// a wider Last in one workgroup would leave its 4 waves hashing a thousand leaves each while the other CUs idle --
+// from there on the Merkle forest build (merkle.hip), which spreads every level over the grid, makes the trees and
+// verify_last_root_cmp_kernel compares the roots.
+constexpr uint32_t kLastLdsMax = 1024, kLastThreads = 256;
+__global__ __launch_bounds__(kLastThreads) void verify_last_root_batch_kernel(const uint8_t* __restrict__ arena,
+                                                                              uint64_t o_last, uint32_t n_last,
+                                                                              uint32_t o_blocks, uint32_t block,
+                                                                              uint32_t o_root, uint8_t* __restrict__ ok) {
+  __shared__ __attribute__((aligned(16))) Digest lds[kLastLdsMax];
+  const uint32_t k = blockIdx.x, t = threadIdx.x;
+  const uint8_t* vals = arena + o_last + (uint64_t)32 * k * n_last;
+  for (uint32_t i = t; i < n_last; i += kLastThreads) lds[i] = hash_leaf32(vals + 32 * i);
+  __syncthreads();
+  for (uint32_t width = n_last / 2; width >= 1; width /= 2) {  // (width <= kLastLdsMax / 2 = 2 kLastThreads)
+    const uint32_t i0 = t, i1 = t + kLastThreads;
+    Digest r0, r1;
+    if (i0 < width) r0 = hash_pair(lds[2 * i0], lds[2 * i0 + 1]);
+    if (i1 < width) r1 = hash_pair(lds[2 * i1], lds[2 * i1 + 1]);
+    __syncthreads();
+    if (i0 < width) lds[i0] = r0;
+    if (i1 < width) lds[i1] = r1;
+    __syncthreads();
+  }
+  if (t == 0) {
+    const Digest want = load_digest(reinterpret_cast<const Digest*>(arena + o_blocks + (size_t)k * block + o_root));
+    uint32_t diff = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) diff |= lds[0].h[w] ^ want.h[w];
+    ok[k] = diff == 0;
+  }
+}
+
+// The wide route's compare: tree k's root in the forest against the root in proof k's block, one lane per proof.
+__global__ __launch_bounds__(kThreads) void verify_last_root_cmp_kernel(const uint8_t* __restrict__ arena,
+                                                                         const uint32_t* __restrict__ nodes,
+                                                                         uint64_t stride_words, uint64_t root_word,
+                                                                         uint32_t nb, uint32_t o_blocks, uint32_t block,
+                                                                         uint32_t o_root, uint8_t* __restrict__ ok) {
+  const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= nb) return;
+  const Digest got = load_digest(reinterpret_cast<const Digest*>(nodes + k * stride_words + root_word));
+  const Digest want = load_digest(reinterpret_cast<const Digest*>(arena + o_blocks + (size_t)k * block + o_root));
+  uint32_t diff = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) diff |= got.h[w] ^ want.h[w];
+  ok[k] = diff == 0;
+}
+
+// What prove_low_degree makes of (n, max_deg_plus_1, excl) (fri.rs:46-224; fri.hip fri_check), and where a
+// proof's parts are in its block: the roots first -- the caller's merkle_roots[b], then each layer's root2 --
+// then each layer's openings.  The Last values of a chunk are side by side after the blocks (the forest build
+// takes contiguous trees).
+struct FriShape {
+  uint32_t depth = 0, layers = 0;  // log2 n; Middle layers
+  uint64_t n = 0, n_last = 0, m = 0, n_adm = 0, n_rest = 0;  // m: the bound the Last element is checked against
+  bool last_refused = false;  // the parameters alone refuse every Last (fri.rs:348-351, :359, split_off)
+  bool wide = false;          // n_last > kLastLdsMax
+  size_t o_col_leaf[kMaxLayers], o_col_nodes[kMaxLayers], o_poly_leaf[kMaxLayers], o_poly_nodes[kMaxLayers];
+  size_t block = 0;
+  uint32_t col_depth(uint32_t l) const { return depth - 2 * l - 2; }
+  uint32_t poly_depth(uint32_t l) const { return depth - 2 * l; }
+  size_t o_root(uint32_t slot) const { return 32 * (size_t)slot; }  // slot 0: merkle_roots[b]; 1 + l: root2 of layer l
+  size_t paths() const { return (size_t)layers * (kRows + kRows * kPolyPer); }
+  size_t rows() const { return (size_t)layers * kRows; }
+  size_t last_lanes() const { return last_refused ? 0 : 1 + n_rest; }  // ok bytes: the root, then each rest point
+  // a proof's block, Last values (with the wide route's tree nodes), records and ok bytes
+  size_t staged() const { return block + 32 * n_last * (wide ? 3 : 1) + 32 * (paths() + rows()) + paths() + rows() + last_lanes(); }
+  size_t matrix_bytes() const { return last_refused ? 0 : 32 * m * n_rest; }
+};
+
+// get_pseudorandom_indices takes this modulus and exclusion (fri/src/utils.rs:88, :101; api.hip).
+bool sampler_takes(uint64_t modulus, uint32_t excl) {
+  if (modulus >= ((uint64_t)1 << 24) || excl == 1) return false;
+  if (excl == 0) return modulus > 0;
+  return modulus * (excl - 1) <= 0xFFFFFFFFull && modulus * (excl - 1) / excl > 0;
+}
+
+// False where the chain cannot take the parameters at all (every proof then goes to the single-proof verifier):
+// n = the root's order (a power of two, at most 2^28).
+bool plan_fri_shape(uint64_t n, size_t max_deg_plus_1, uint32_t excl, size_t limit, FriShape& s) {
+  if (excl == 1 || n == 0) return false;
+  s.n = n;
+  while (((uint64_t)1 << s.depth) < n) ++s.depth;
+  uint64_t m = n;
+  size_t deg = max_deg_plus_1;
+  while (deg > 16) {
+    if (m < 8 || !sampler_takes(m / 4, excl)) return false;
+    m /= 4;
+    deg /= 4;
+    if (++s.layers + 1 > kMaxLayers) return false;
+  }
+  s.n_last = m;
+  s.m = deg;
+  s.n_adm = excl ? m - (m + excl - 1) / excl : m;
+  s.last_refused = s.m < 16 / 2 || s.n_last <= s.m || s.n_adm < s.m;
+  s.n_rest = s.last_refused ? 0 : s.n_adm - s.m;
+  s.wide = s.n_last > kLastLdsMax;
+  if (s.matrix_bytes() > limit / 4) return false;
+  size_t at = 32 * (1 + (size_t)s.layers);
+  auto take = [&](size_t bytes) {
+    const size_t o = at;
+    at += bytes;
+    return o;
+  };
+  for (uint32_t l = 0; l < s.layers; ++l) {
+    s.o_col_leaf[l] = take((size_t)kRows * 32);
+    s.o_col_nodes[l] = take((size_t)kRows * 32 * s.col_depth(l));
+    s.o_poly_leaf[l] = take((size_t)kRows * kPolyPer * 32);
+    s.o_poly_nodes[l] = take((size_t)kRows * kPolyPer * 32 * s.poly_depth(l));
+  }
+  s.block = at;
+  // (the records hold 32-bit offsets: a chunk of one proof must stay under them with the call's constants)
+  return s.matrix_bytes() + s.staged() < ((size_t)3 << 30);
+}
+
+// The handle's structure is exactly what the parameters imply: every length the packing and the kernels assume.
+bool fri_in_shape(const std::vector<FriIn>& fri, const FriShape& s) {
+  if (fri.size() != (size_t)s.layers + 1) return false;
+  for (uint32_t l = 0; l < s.layers; ++l) {
+    const FriIn& f = fri[l];
+    if (f.last || !branches_are(f.col, kRows, 32, s.col_depth(l)) ||
+        !branches_are(f.poly, kRows * kPolyPer, 32, s.poly_depth(l)))
+      return false;
+  }
+  const FriIn& last = fri.back();
+  if (!last.last || last.last_vals.size() != s.n_last) return false;
+  for (const std::vector<uint8_t>& v : last.last_vals)
+    if (v.size() != 32) return false;
+  return true;
+}
+
+struct FriItem {
+  std::vector<FriIn> fri;
+  bool chain = false, fallback = false, last_ok = false;
+  stark_status st = STARK_OK;
+  uint32_t reasons = 0;
+  std::vector<std::vector<size_t>> ys;  // per Middle layer
+};
+
+struct FriChunkPlan {
+  size_t o_paths, o_rows, o_blocks, o_last, o_ok, total;
+  size_t n_paths, n_rows, n_last_ok;
+};
+FriChunkPlan plan_fri_chunk(const FriShape& s, size_t base, size_t nb, bool device_last) {
+  FriChunkPlan p;
+  p.n_paths = nb * s.paths();
+  p.n_rows = nb * s.rows();
+  p.n_last_ok = device_last ? nb * s.last_lanes() : 0;
+  p.o_paths = base;
+  p.o_rows = p.o_paths + 32 * p.n_paths;
+  p.o_blocks = p.o_rows + 32 * p.n_rows;
+  p.o_last = p.o_blocks + nb * s.block;
+  p.o_ok = align256(p.o_last + (device_last && !s.last_refused ? nb * 32 * s.n_last : 0));
+  p.total = p.o_ok + align256(p.n_paths + p.n_rows + p.n_last_ok);
+  return p;
+}
+
+// Chain proof k of nb: its block (roots first), its records (class-major per layer: the polynomial openings,
+// then the column openings; rows layer-major) and, for the device's Last check, its Last values.
+void pack_fri(const FriShape& s, const FriChunkPlan& p, size_t nb, size_t k, const uint8_t* merkle_root,
+              const FriItem& it, bool with_last, uint8_t* img) {
+  const size_t blk = p.o_blocks + k * s.block;
+  uint8_t* const b = img + blk;
+  memcpy(b, merkle_root, 32);
+  for (uint32_t l = 0; l < s.layers; ++l) {
+    memcpy(b + s.o_root(1 + l), it.fri[l].root2, 32);
+    put_branches(b + s.o_col_leaf[l], b + s.o_col_nodes[l], it.fri[l].col);
+    put_branches(b + s.o_poly_leaf[l], b + s.o_poly_nodes[l], it.fri[l].poly);
+  }
+  if (with_last) {
+    uint8_t* v = img + p.o_last + k * 32 * s.n_last;
+    for (const std::vector<uint8_t>& x : it.fri.back().last_vals) {
+      memcpy(v, x.data(), 32);
+      v += 32;
+    }
+  }
+  PathRec* paths = reinterpret_cast<PathRec*>(img + p.o_paths);
+  RowRec* rows = reinterpret_cast<RowRec*>(img + p.o_rows);
+  auto u = [](size_t x) { return (uint32_t)x; };
+  size_t cls = 0;
+  uint64_t deg = s.n;
+  for (uint32_t l = 0; l < s.layers; ++l, deg /= 4) {
+    const size_t root_l = blk + s.o_root(l), root2 = blk + s.o_root(1 + l);
+    const uint32_t pd = s.poly_depth(l), cd = s.col_depth(l);
+    for (uint32_t i = 0; i < kRows; ++i)
+      for (uint32_t j = 0; j < kPolyPer; ++j) {
+        const size_t q = kPolyPer * i + j;
+        paths[cls + k * kRows * kPolyPer + q] = PathRec{u(root_l), u(blk + s.o_poly_leaf[l] + 32 * q),
+                                                        u(blk + s.o_poly_nodes[l] + 32 * pd * q),
+                                                        u(j * (deg / 4) + it.ys[l][i]), 32, pd, 0, 0};
+      }
+    cls += nb * kRows * kPolyPer;
+    for (uint32_t i = 0; i < kRows; ++i) {
+      paths[cls + k * kRows + i] = PathRec{u(root2), u(blk + s.o_col_leaf[l] + 32 * i),
+                                           u(blk + s.o_col_nodes[l] + 32 * cd * i), u(it.ys[l][i]), 32, cd, 0, 0};
+      rows[((size_t)l * nb + k) * kRows + i] = RowRec{u(root_l), u(blk + s.o_col_leaf[l] + 32 * i),
+                                                      u(blk + s.o_poly_leaf[l] + 32 * kPolyPer * i), u(it.ys[l][i]), l, 0, 0, 0};
+    }
+    cls += nb * kRows;
+  }
+}
+
+}  // namespace
+
+// statuses / reasons of entries [0, batch) (both non-null here).
+static stark_status verify_fri_batch(stark_ctx* ctx, const uint8_t* merkle_roots, const uint64_t root_of_unity[4],
+                                     const stark_fri_proof* const* proofs, uint32_t batch, size_t max_deg_plus_1,
+                                     uint32_t excl, stark_status* statuses, uint32_t* reasons) {
+  const FieldHost& F = FieldHost::get();
+  PhaseClock clk("verify_low_degree_batch");
+  const HostFp root = F.from_canonical(root_of_unity);
+  // The root's order as verify_fri finds it: a power of two up to 2^28, else no proof of the call has a chain.
+  uint64_t n = 1;
+  for (HostFp t = root; n <= ((uint64_t)1 << 28) && !FieldHost::eq(t, F.one()); t = F.mul(t, t)) n *= 2;
+  const size_t limit = std::min<size_t>(ctx->verify_batch_limit ? ctx->verify_batch_limit : kDefaultVerifyBatchLimit,
+                                        (size_t)3 << 30);
+  FriShape s;
+  const bool chain_ok = n <= ((uint64_t)1 << 28) && plan_fri_shape(n, max_deg_plus_1, excl, limit, s);
+  const bool device_last = (ctx->verify_batch_last ? ctx->verify_batch_last : kDefaultVerifyLast) == 2;
+  const bool last_dev = device_last && chain_ok && !s.last_refused;  // the Last kernels run
+  hipStream_t stream = ctx->stream;
+  // The call's constants at the image's start: the layers' roots of unity and sizes, the Last element's m
+  // interpolation points and weights, then the check matrix (made on the device, never uploaded).
+  const size_t o_lroot = 0, o_ldeg = o_lroot + 32 * kMaxLayers, o_xi = o_ldeg + 8 * kMaxLayers, o_wi = o_xi + 32 * 16,
+               o_mat = o_wi + 32 * 16;
+  const size_t base = chain_ok ? align256(o_mat + (last_dev ? s.matrix_bytes() : 0)) : 0;
+  HostFp w_last = root;  // root^(4^layers): the Last element's root of unity
+  if (chain_ok)
+    for (uint32_t l = 0; l < s.layers; ++l) w_last = F.pow_u64(w_last, 4);
+  const size_t per_chunk = chain_ok ? std::max<size_t>(1, (limit > base ? limit - base : 0) / s.staged()) : batch;
+  bool consts_up = false;
+  const size_t workers = host_threads();
+  for (uint32_t b0 = 0; b0 < batch;) {
+    const uint32_t b1 = (uint32_t)std::min<size_t>(batch, (size_t)b0 + per_chunk);
+    const size_t cn = b1 - b0;
+    std::vector<FriItem> items(cn);
+    // View, screen and sample each entry (the indices come from the roots as given, per proof on the workers).
+    auto screen_one = [&](size_t i) {
+      FriItem& it = items[i];
+      const stark_fri_proof* h = proofs[b0 + i];
+      if (!h || !view_fri(*h, it.fri)) {
+        it.st = STARK_ERR_BAD_ARG;
+        it.reasons = STARK_VERIFY_FAIL_SINGLE;
+        return;
+      }
+      it.fallback = true;
+      if (!chain_ok || !fri_in_shape(it.fri, s)) return;
+      it.ys.resize(s.layers);
+      uint64_t deg = s.n;
+      for (uint32_t l = 0; l < s.layers; ++l, deg /= 4)
+        if (!sampler(it.fri[l].root2, deg / 4, kRows, excl, it.ys[l])) return;
+      it.fallback = false;
+      it.chain = true;
+    };
+    if (2 * cn < workers) {
+      for (size_t i = 0; i < cn; ++i) screen_one(i);
+    } else {
+      std::atomic<size_t> next{0};
+      host_parallel((unsigned)std::min(workers, cn), [&](unsigned) {
+        for (size_t i; (i = next.fetch_add(1)) < cn;) screen_one(i);
+      });
+    }
+    clk.mark("handles viewed and screened");
+    std::vector<size_t> chain;
+    for (size_t i = 0; i < cn; ++i)
+      if (items[i].chain) chain.push_back(i);
+    const size_t nb = chain.size();
+    if (nb > 0) {
+      const FriChunkPlan p = plan_fri_chunk(s, base, nb, device_last);
+      const FriChunkPlan widest = plan_fri_chunk(s, base, std::min<size_t>(per_chunk, batch), device_last);
+      STARK_TRY(ensure_buf(ctx, ctx->verify_batch, widest.total));
+      uint8_t* img = nullptr;
+      STARK_TRY(ctx_pinned(ctx, 7, widest.total, (void**)&img));
+      uint8_t* const d_img = (uint8_t*)ctx->verify_batch.ptr;
+      std::vector<HostFp> xi, wi;
+      if (!consts_up) {
+        HostFp rt = root;
+        uint64_t dg = s.n;
+        for (uint32_t l = 0; l < kMaxLayers; ++l) {
+          memcpy(img + o_lroot + 32 * l, rt.v, 32);
+          memcpy(img + o_ldeg + 8 * l, &dg, 8);
+          rt = F.pow_u64(rt, 4);
+          dg = std::max<uint64_t>(dg / 4, 1);
+        }
+        memset(img + o_xi, 0, 2 * 32 * 16);
+        if (last_dev) {  // x_i = w^pos(i), w_i = 1 / prod_(j != i) (x_i - x_j), i < m <= 16
+          for (uint64_t i = 0; i < s.m; ++i) xi.push_back(F.pow_u64(w_last, admissible_pos(i, excl)));
+          // (one field inversion for all m denominators: the products before each, the inverse of the whole, then
+          // back down -- an inversion is some 380 products, sixteen of them were most of the call's fixed cost)
+          std::vector<HostFp> den(s.m, F.one()), before(s.m + 1, F.one());
+          for (uint64_t i = 0; i < s.m; ++i) {
+            for (uint64_t j = 0; j < s.m; ++j)
+              if (j != i) den[i] = F.mul(den[i], F.sub(xi[i], xi[j]));  // (distinct powers below the order: not 0)
+            before[i + 1] = F.mul(before[i], den[i]);
+          }
+          HostFp inv_rest = F.inv(before[s.m]);
+          wi.assign(s.m, F.one());
+          for (uint64_t i = s.m; i-- > 0;) {
+            wi[i] = F.mul(inv_rest, before[i]);
+            inv_rest = F.mul(inv_rest, den[i]);
+          }
+          for (uint64_t i = 0; i < s.m; ++i) {
+            memcpy(img + o_xi + 32 * i, xi[i].v, 32);
+            memcpy(img + o_wi + 32 * i, wi[i].v, 32);
+          }
+        }
+      }
+      {
+        std::atomic<size_t> next{0};
+        host_parallel((unsigned)std::min(workers, nb), [&](unsigned) {
+          for (size_t k; (k = next.fetch_add(1)) < nb;)
+            pack_fri(s, p, nb, k, merkle_roots + 32 * (size_t)(b0 + chain[k]), items[chain[k]], last_dev, img);
+        });
+      }
+      clk.mark("openings packed");
+      {
+        // (the matrix region [o_mat, base) is the device's own: the upload goes around it)
+        if (!consts_up) STARK_HIP(ctx, hipMemcpyAsync(d_img, img, o_mat, hipMemcpyHostToDevice, stream));
+        const size_t end = last_dev ? p.o_last + nb * 32 * s.n_last : p.o_blocks + nb * s.block;
+        STARK_HIP(ctx, hipMemcpyAsync(d_img + base, img + base, end - base, hipMemcpyHostToDevice, stream));
+      }
+      auto blocks = [](size_t lanes) { return dim3((unsigned)((lanes + kThreads - 1) / kThreads)); };
+      auto u = [](size_t x) { return (uint32_t)x; };
+      LastArgs A{};
+      if (last_dev) {
+        A.n_last = u(s.n_last);
+        A.m = u(s.m);
+        A.n_rest = u(s.n_rest);
+        A.excl = excl;
+        A.o_xi = u(o_xi);
+        A.o_mat = u(o_mat);
+        A.w = to_dev(w_last);
+        A.r2m = to_dev(F.from_canonical(F.one().v));
+        A.one = to_dev(F.one());
+        if (!consts_up && s.n_rest > 0)
+          hipLaunchKernelGGL(verify_last_matrix_kernel, blocks(s.m * s.n_rest), dim3(kThreads), 0, stream, d_img,
+                             (const fe*)(d_img + o_wi), A);
+      }
+      consts_up = true;
+      uint8_t* const d_ok = d_img + p.o_ok;
+      if (p.n_paths > 0)
+        hipLaunchKernelGGL(verify_paths_batch_kernel, blocks(p.n_paths), dim3(kThreads), 0, stream, d_img,
+                           (const PathRec*)(d_img + p.o_paths), (uint32_t)p.n_paths, d_ok);
+      if (p.n_rows > 0) {
+        RowConsts K;
+        K.r2m = to_dev(F.from_canonical(F.one().v));  // (R mod p) R = R^2
+        K.one = to_dev(F.one());
+        K.inv4 = to_dev(F.inv(F.from_u64(4)));
+        for (int j = 0; j < 4; ++j) K.quartic[j] = to_dev(F.pow_u64(root, s.n / 4 * (uint64_t)j));
+        hipLaunchKernelGGL(verify_fri_rows_batch_kernel, blocks(p.n_rows), dim3(kThreads), 0, stream, d_img,
+                           (const RowRec*)(d_img + p.o_rows), (uint32_t)p.n_rows, (const fe*)(d_img + o_lroot),
+                           (const uint64_t*)(d_img + o_ldeg), K, d_ok + p.n_paths);
+      }
+      STARK_HIP(ctx, hipGetLastError());
+      if (last_dev) {
+        // ok bytes of the Last elements: nb roots, then nb x n_rest rest points.
+        uint8_t* const d_root_ok = d_ok + p.n_paths + p.n_rows;
+        if (!s.wide) {
+          hipLaunchKernelGGL(verify_last_root_batch_kernel, dim3((unsigned)nb), dim3(kLastThreads), 0, stream, d_img,
+                             (uint64_t)p.o_last, u(s.n_last), u(p.o_blocks), u(s.block), u(s.o_root(s.layers)),
+                             d_root_ok);
+        } else {
+          if (!ctx->verify_forest) STARK_TRY(stark_merkle_forest_new(ctx, &ctx->verify_forest));
+          STARK_TRY(forest_build(ctx, ctx->verify_forest, d_img + p.o_last, s.n_last, 32, (uint32_t)nb, stream));
+          uint64_t stride_words = 0, root_word = 0;
+          const uint32_t* nodes = forest_nodes_dev(ctx->verify_forest, &stride_words, &root_word);
+          hipLaunchKernelGGL(verify_last_root_cmp_kernel, blocks(nb), dim3(kThreads), 0, stream, d_img, nodes,
+                             stride_words, root_word, u(nb), u(p.o_blocks), u(s.block), u(s.o_root(s.layers)),
+                             d_root_ok);
+        }
+        if (s.n_rest > 0)
+          hipLaunchKernelGGL(verify_last_degree_batch_kernel, blocks(nb * s.n_rest), dim3(kThreads), 0, stream, d_img,
+                             (uint64_t)p.o_last, u(nb), A, d_root_ok + nb);
+        STARK_HIP(ctx, hipGetLastError());
+      }
+      const size_t n_ok = p.n_paths + p.n_rows + p.n_last_ok;
+      if (n_ok > 0) STARK_HIP(ctx, hipMemcpyAsync(img + p.o_ok, d_ok, n_ok, hipMemcpyDeviceToHost, stream));
+      clk.mark("upload, launches, download enqueued");
+      if (!device_last && !s.last_refused) {
+        // The Last elements beside the device work, one proof per task (fri_last_check with what the Middle layers
+        // leave: the last root2 -- the caller's root without layers --, root^(4^layers), the bound over 4^layers).
+        std::atomic<size_t> next{0};
+        host_parallel((unsigned)std::min(workers, nb), [&](unsigned) {
+          for (size_t k; (k = next.fetch_add(1)) < nb;) {
+            FriItem& it = items[chain[k]];
+            const uint8_t* m_root =
+                s.layers ? it.fri[s.layers - 1].root2 : merkle_roots + 32 * (size_t)(b0 + chain[k]);
+            it.last_ok = fri_last_check(it.fri.back(), m_root, w_last, s.m, excl) == STARK_OK;
+          }
+        });
+        clk.mark("Last elements (host)");
+      }
+      STARK_HIP(ctx, hipStreamSynchronize(stream));
+      clk.mark("device joined");
+      // A chain proof has the exact structure the parameters imply and the sampler took each of its roots, so the
+      // single-proof verifier has no STARK_ERR_BAD_ARG left for it (each of verify_fri's is a shape or order
+      // condition screened above): it returns STARK_ERR_CHECK at its first failed check and STARK_OK when none
+      // fails, so the status is STARK_OK iff every path and row byte and the Last element's check hold.
+      const uint8_t* ok = img + p.o_ok;
+      auto any_bad = [&](size_t first, size_t count) {
+        for (size_t i = 0; i < count; ++i)
+          if (!ok[first + i]) return true;
+        return false;
+      };
+      for (size_t k = 0; k < nb; ++k) {
+        FriItem& it = items[chain[k]];
+        uint32_t why = 0;
+        size_t cls = 0;
+        for (uint32_t l = 0; l < s.layers; ++l) {
+          if (any_bad(cls + k * kRows * kPolyPer, kRows * kPolyPer)) why |= STARK_VERIFY_FAIL_FRI_PATHS;
+          cls += nb * kRows * kPolyPer;
+          if (any_bad(cls + k * kRows, kRows)) why |= STARK_VERIFY_FAIL_FRI_PATHS;
+          cls += nb * kRows;
+          if (any_bad(p.n_paths + ((size_t)l * nb + k) * kRows, kRows)) why |= STARK_VERIFY_FAIL_FRI_ROWS;
+        }
+        bool last_ok = false;  // (the parameters alone may refuse every Last)
+        if (!s.last_refused) {
+          const size_t at = p.n_paths + p.n_rows;
+          last_ok = device_last ? !any_bad(at + k, 1) && !any_bad(at + nb + k * s.n_rest, s.n_rest) : it.last_ok;
+        }
+        if (!last_ok) why |= STARK_VERIFY_FAIL_FRI_LAST;
+        it.reasons = why;
+        it.st = why ? STARK_ERR_CHECK : STARK_OK;
+      }
+    }
+    // Everything else that has a handle: the single-proof verifier's status.
+    for (size_t i = 0; i < cn; ++i) {
+      FriItem& it = items[i];
+      if (it.fallback) {
+        it.st = verify_fri_single(merkle_roots + 32 * (size_t)(b0 + i), root, it.fri, max_deg_plus_1, excl);
+        it.reasons = it.st == STARK_OK ? 0 : STARK_VERIFY_FAIL_SINGLE;
+      }
+      statuses[b0 + i] = it.st;
+      reasons[b0 + i] = it.reasons;
+    }
+    clk.mark("statuses composed");
+    b0 = b1;
+  }
+  return STARK_OK;
+}
+
 }  // namespace stark
 
 using namespace stark;
 
 extern "C" {
+
+stark_status stark_verify_low_degree_batch(stark_ctx* ctx, const uint8_t* merkle_roots, const uint64_t root_of_unity[4],
+                                           const stark_fri_proof* const* proofs, uint32_t batch, size_t max_deg_plus_1,
+                                           uint32_t exclude_multiples_of, stark_status* statuses, uint32_t* reasons) {
+  if (!ctx || !merkle_roots || !root_of_unity || !proofs || batch > 65535) return STARK_ERR_BAD_ARG;
+  if (batch == 0) return STARK_OK;  // (nothing to read, the handles included)
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<stark_status> sts(batch, STARK_OK);
+  std::vector<uint32_t> why(batch, 0);
+  STARK_TRY(verify_fri_batch(ctx, merkle_roots, root_of_unity, proofs, batch, max_deg_plus_1, exclude_multiples_of,
+                             sts.data(), why.data()));
+  if (reasons) memcpy(reasons, why.data(), sizeof(uint32_t) * batch);
+  if (statuses) {
+    memcpy(statuses, sts.data(), sizeof(stark_status) * batch);
+    return STARK_OK;
+  }
+  for (uint32_t b = 0; b < batch; ++b)
+    if (sts[b] != STARK_OK) return sts[b];
+  return STARK_OK;
+}
 
 stark_status stark_verify_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
                                              const uint8_t* const* public_wires, size_t n_public,

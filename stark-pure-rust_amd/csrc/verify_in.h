@@ -70,6 +70,10 @@ stark_status verify_interp2(stark_ctx* ctx, const PreparedCircuit& c, const std:
                             const VerifyDomain& d, const std::vector<HostFp>& bx, std::vector<HostFp>& interp2);
 // r from a_root (utils.rs:272-290) and k from m_root (verify.rs:164-173); false where the sampler panics.
 bool verify_challenges(const ProofIn& pr, uint64_t prec, HostFp r[3], HostFp kk[11]);
+// verify_low_degree_proof (fri.rs:226-404) on a parsed Vec<FriProof>: what stark_verify_low_degree_proof returns
+// for these parts (root: the root of unity's Montgomery image).
+stark_status verify_fri_single(const uint8_t merkle_root[32], const HostFp& root, const std::vector<FriIn>& proof,
+                               size_t max_deg_plus_1, uint32_t excl);
 // The FriProof::Last element's checks (fri.rs:346-403) against the tree root, root of unity and degree bound
 // that the Middle layers before it leave.
 stark_status fri_last_check(const FriIn& last, const uint8_t m_root[32], const HostFp& root, size_t max_deg_plus_1,

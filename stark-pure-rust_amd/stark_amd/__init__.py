@@ -201,6 +201,11 @@ _SIGNATURES = {
     "stark_r1cs_proof_from_parts": ([_u8p, _u8p, _u8p, _vp, _vp, _vp, ctypes.c_size_t, _u8p, ctypes.c_size_t,
                                      ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_ctx_set_verify_batch_transcript": ([_vp, ctypes.c_uint32], ctypes.c_int),
+    "stark_ctx_set_verify_batch_last": ([_vp, ctypes.c_uint32], ctypes.c_int),
+    "stark_fri_proof_from_parts": ([_vp, ctypes.c_size_t, _u8p, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_verify_low_degree_batch": ([_vp, _u8p, _u64p, ctypes.POINTER(_vp), ctypes.c_uint32, ctypes.c_size_t,
+                                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
     "stark_verify_r1cs_bytes": ([_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                  ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
     "stark_group_create": ([ctypes.POINTER(ctypes.c_int), ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
@@ -376,6 +381,11 @@ class Context:
         """Who derives the indices, challenges and records of R1csCircuit.verify_batch's chain proofs: 1 the
         host, 2 the device (one workgroup per proof), 0 the library's default.  Same statuses and reasons."""
         self.check(self.lib.stark_ctx_set_verify_batch_transcript(self.h, int(mode)), "set_verify_batch_transcript")
+
+    def set_verify_batch_last(self, mode: int):
+        """Who checks the Last elements of verify_low_degree_batch's chain proofs: 1 the host workers, 2 the
+        device (one shared check matrix), 0 the library's default.  Same statuses and reasons."""
+        self.check(self.lib.stark_ctx_set_verify_batch_last(self.h, int(mode)), "set_verify_batch_last")
 
     def memory(self) -> dict:
         """{'cached': bytes of cached tables, 'cache_limit': their cap, 'resident': all device bytes held}."""
@@ -761,6 +771,57 @@ class FriProofList:
 
     def layers(self) -> list:
         return json.loads(self.to_json())
+
+    def parts(self) -> dict:
+        """Everything from_parts takes: {"layers": [{"root2", "column", "poly"}], "last": bytes}, each set of
+        openings as {"leaves", "nodes", "k", "leaf_len", "depth"}."""
+        return self.parts_of_list(self.layers())
+
+    @staticmethod
+    def parts_of_list(proof: list) -> dict:
+        """A parsed Vec<FriProof> (serde_json's list) as from_parts' parts.  A handle holds the Middle layers then
+        one Last, uniform openings per set and 32-byte Last values: anything else is StarkError(3), as
+        stark_amd.verify.verify_low_degree_proof refuses it."""
+        def uniform(brs):
+            ll = len(brs[0]["leaf"]) if brs else 32
+            d = len(brs[0]["nodes"]) if brs else 0
+            if any(len(b["leaf"]) != ll or len(b["nodes"]) != d or any(len(n) != 32 for n in b["nodes"]) for b in brs):
+                raise StarkError(3, "FriProofList.from_parts", "openings of unequal shape")
+            return {"leaves": b"".join(bytes(b["leaf"]) for b in brs),
+                    "nodes": b"".join(bytes(n) for b in brs for n in b["nodes"]), "k": len(brs), "leaf_len": ll,
+                    "depth": d}
+        if not proof or "Last" not in proof[-1] or any("Middle" not in x for x in proof[:-1]):
+            raise StarkError(3, "FriProofList.from_parts", "Middle layers then one Last layer expected")
+        last = [bytes(v) for v in proof[-1]["Last"]["last"]]
+        if any(len(v) != 32 for v in last):
+            raise StarkError(3, "FriProofList.from_parts", "a Last value is not 32 bytes")
+        return {"layers": [{"root2": bytes(x["Middle"]["root2"]), "column": uniform(x["Middle"]["column_branches"]),
+                            "poly": uniform(x["Middle"]["poly_branches"])} for x in proof[:-1]],
+                "last": b"".join(last)}
+
+    @classmethod
+    def from_parts(cls, layers, lib=None) -> "FriProofList":
+        """A handle over copies of a Vec<FriProof>'s parts (stark_fri_proof_from_parts; host only): `layers` is
+        what parts() returns, or a parsed serde list.  What verify_low_degree_batch takes."""
+        from .verify import _Branches, _FriLayer
+        lib = lib or load_library()
+        parts = cls.parts_of_list(layers) if isinstance(layers, list) else layers
+
+        def br(b):
+            return _Branches(b["leaves"], b["nodes"], b["k"], b["leaf_len"], b["depth"])
+        mids = parts["layers"]
+        arr = (_FriLayer * max(len(mids), 1))()
+        for i, m in enumerate(mids):
+            if len(m["root2"]) != 32:
+                raise StarkError(3, "FriProofList.from_parts", "root2 is not 32 bytes")
+            arr[i] = _FriLayer(m["root2"], br(m["column"]), br(m["poly"]))
+        last = parts["last"]
+        h = _vp()
+        rc = lib.stark_fri_proof_from_parts(ctypes.cast(arr, ctypes.c_void_p), len(mids), last, len(last) // 32,
+                                            ctypes.byref(h))
+        if rc != 0:
+            raise StarkError(rc, "stark_fri_proof_from_parts")
+        return cls(lib, h)
 
 
 # ---- host-side helpers with the reference names ------------------------------

@@ -73,6 +73,43 @@ def verify_low_degree_proof(merkle_root: bytes, root_of_unity: int, proof, max_d
     return _result(rc, "verify_low_degree_proof")
 
 
+def verify_low_degree_batch(ctx: Context, roots, root_of_unity: int, proofs, max_deg_plus_1: int,
+                            exclude_multiples_of: int) -> list:
+    """verify_low_degree_proof for every (roots[b], proofs[b]) of one (root of unity, degree bound, exclusion)
+    through one chain of launches (stark_verify_low_degree_batch): [(status, reasons)] per proof, in
+    R1csCircuit.verify_batch's convention -- status 0 = verifies, 8 = invalid, 3 = malformed; reasons = the OR of
+    FAIL_FRI_PATHS / FAIL_FRI_ROWS / FAIL_FRI_LAST for a proof checked on the GPU, FAIL_SINGLE for any other entry
+    that is not 0.  `proofs` holds FriProofList handles, parsed serde lists or texts (made into handles:
+    FriProofList.from_parts), or None.  A list that is not Middle layers then one Last cannot be a handle: it is
+    status 3 with FAIL_SINGLE here, as verify_low_degree_proof raises StarkError(3) for it.  Raises only for an error
+    of the call as a whole."""
+    from . import FriProofList
+    n = len(proofs)
+    if len(roots) != n:
+        raise StarkError(3, "verify_low_degree_batch", "one Merkle root per proof expected")
+    if n == 0:
+        return []
+    handles = []
+    for p in proofs:
+        if isinstance(p, (str, bytes)):
+            p = json.loads(p)
+        if isinstance(p, list):
+            try:
+                p = FriProofList.from_parts(p, ctx.lib)
+            except StarkError:
+                p = None
+        handles.append(p)
+    blob = b"".join(bytes(r).ljust(32, b"\0")[:32] for r in roots)
+    hs = (ctypes.c_void_p * n)(*[None if p is None else p.h for p in handles])
+    sts = (ctypes.c_int * n)()
+    why = (ctypes.c_uint32 * n)()
+    rou = _limbs(root_of_unity)
+    rc = ctx.lib.stark_verify_low_degree_batch(ctx.h, blob, rou.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), hs, n,
+                                               max_deg_plus_1, exclude_multiples_of, sts, why)
+    ctx.check(rc, "verify_low_degree_batch")
+    return [(int(sts[b]), int(why[b])) for b in range(n)]
+
+
 def _json_bytes(proof) -> bytes:
     if isinstance(proof, bytes):
         return proof
