@@ -46,8 +46,9 @@ extern "C" {
  * 10: stark_verify_r1cs_circuit_batch_proofs, stark_r1cs_proof_from_parts,
  *     stark_ctx_set_verify_batch_transcript.
  * 11: stark_interp_plan_*, stark_lagrange_interp_batch.
- * 12: stark_fri_proof_from_parts, stark_verify_low_degree_batch, stark_ctx_set_verify_batch_last. */
-#define STARK_ABI_VERSION 12u
+ * 12: stark_fri_proof_from_parts, stark_verify_low_degree_batch, stark_ctx_set_verify_batch_last.
+ * 13: stark_check_r1cs_circuit(_batch), stark_r1cs_failure. */
+#define STARK_ABI_VERSION 13u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -497,6 +498,49 @@ stark_status stark_prove_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_cir
                                             const uint8_t* const* wtns, const size_t* wtns_lens, uint32_t batch,
                                             stark_r1cs_proof** out /* batch handles */,
                                             stark_status* statuses /* batch entries, or NULL */);
+
+/* Witness check (no reference counterpart: the reference meets an unsatisfying witness as a divisibility assert at
+ * the end of its prover, r1cs-stark/src/utils.rs:379-418): which constraints of a prepared circuit `batch` witnesses
+ * fail, with A.w, B.w and C.w of each, without proving anything.  The check reads the circuit's slot layout,
+ * coefficients and slot wires and the decoded witnesses: no witness column, no extension (the circuit's LDE is
+ * neither needed nor read) and no tree.  Every circuit stark_r1cs_circuit_new returned can be checked, whatever a
+ * proof on it would return.
+ * Errors of the call as a whole are stark_prove_r1cs_circuit_batch's -- a null ctx, circuit, wtns or wtns_lens, a
+ * circuit prepared on another context or for world != 1, batch > 65535 -- and cap > 0 with failures == NULL: they
+ * return STARK_ERR_BAD_ARG, nothing is read or written and no device call is made; batch == 0 returns STARK_OK.
+ * Per witness the prover's host checks decide first: a null or malformed .wtns, too few values or witness[0] != 1
+ * give STARK_ERR_BAD_ARG with n_failed[b] = 0 and no failure written.  Otherwise the status is STARK_OK when every
+ * constraint holds and STARK_ERR_CHECK when n_failed[b] > 0.  The values are the prover's: coefficients and
+ * witness values of any 32 bytes are reduced mod p (from_bytes_le), a witness of field_size 8, 16 or 32 is
+ * accepted, values behind the circuit's wires are ignored; a constraint without terms holds and an empty factor
+ * has value 0.
+ * n_failed[b] is the exact number of constraints with A.w B.w != C.w (mod p), whatever cap is.
+ * failures[b cap + k], k < min(n_failed[b], cap), are the failing constraints with the smallest indices in
+ * ascending order, each with its three values; entries behind those are not written.
+ * With statuses != NULL the call returns STARK_OK or a device error; with statuses == NULL it returns the first
+ * status in batch order that is not STARK_OK, and the arrays are filled for every witness all the same.  One
+ * witness changes nothing about another, and two calls on the same input give the same bytes.
+ * A chunk's working set per witness is n_wires x 64 B (raw and Montgomery values), one bit per constraint and
+ * min(cap, n_constraints) records; consecutive chunks stay under stark_ctx_set_prove_batch_limit (a limit below
+ * one witness means chunks of one).  The buffers are reused across calls and counted in stark_ctx_memory's
+ * resident_bytes, as is the list of the circuit's long constraints, which the circuit's first check builds and
+ * stark_r1cs_circuit_free frees.  A chunk is staged in pinned host memory (n_wires x 32 B per witness, its counts
+ * and records), which grows to the largest chunk seen, stays for the life of the context and, being host memory,
+ * is not counted there: about half the chunk's device bytes, so the same limit bounds it. */
+typedef struct stark_r1cs_failure {
+  uint32_t constraint;          /* index in the .r1cs file's order */
+  uint32_t reserved;            /* 0 */
+  uint64_t a[4], b[4], c[4];    /* A.w, B.w, C.w mod p: canonical, little-endian limbs, as every element on this ABI */
+} stark_r1cs_failure;
+stark_status stark_check_r1cs_circuit_batch(stark_ctx* ctx, const stark_r1cs_circuit* circuit,
+                                            const uint8_t* const* wtns, const size_t* wtns_lens, uint32_t batch,
+                                            stark_status* statuses /* batch, or NULL */,
+                                            uint32_t* n_failed /* batch, or NULL */,
+                                            stark_r1cs_failure* failures /* batch x cap, or NULL when cap == 0 */,
+                                            uint32_t cap);
+/* The batch of one: the return value is the witness's status. */
+stark_status stark_check_r1cs_circuit(stark_ctx* ctx, const stark_r1cs_circuit* circuit, const uint8_t* wtns,
+                                      size_t wtns_len, uint32_t* n_failed, stark_r1cs_failure* failures, uint32_t cap);
 
 /* ---- multi-GPU four-step NTT building blocks (no reference counterpart;
  * the reference is single-process).  The exchanges are RCCL

@@ -314,6 +314,7 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   hipDeviceSynchronize();  // (work the caller enqueued on its own streams may still read context buffers)
   ctx->tw.clear();  // (~Twiddles frees the tables)
   interp_plans_release_all(ctx);  // (their handles and circuits may be freed after this: they then hold nothing)
+  long_lists_release_all(ctx);
   for (stark_merkle_tree*& t : ctx->trees) {
     stark_merkle_free(t);
     t = nullptr;
@@ -341,7 +342,7 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   ctx->fri_trees.clear();
   for (DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena, &ctx->trace_raw, &ctx->fri_misc,
                      &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena, &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly,
-                     &ctx->prove_batch, &ctx->verify_batch}) {
+                     &ctx->prove_batch, &ctx->verify_batch, &ctx->witness_check}) {
     if (b->ptr) hipFree(b->ptr);
     if (b->ev) hipEventDestroy(b->ev);
   }
@@ -382,6 +383,14 @@ stark_status stark_ctx_set_prove_batch_limit(stark_ctx* ctx, size_t bytes) {
     ctx->prove_batch.last = nullptr;
     for (stark_merkle_forest* f : ctx->r1cs_forests) forest_release(f);
     for (stark_merkle_forest* f : ctx->fri_forests) forest_release(f);
+  }
+  // stark_check_r1cs_circuit_batch's chunks stay under the same cap
+  if (ctx->witness_check.ptr && ctx->witness_check.bytes > cap) {
+    STARK_HIP(ctx, hipDeviceSynchronize());
+    hipFree(ctx->witness_check.ptr);
+    ctx->witness_check.ptr = nullptr;
+    ctx->witness_check.bytes = 0;
+    ctx->witness_check.last = nullptr;
   }
   return STARK_OK;
 }
@@ -429,7 +438,7 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   for (const DevBuf* b : {&ctx->scratch, &ctx->io, &ctx->io2, &ctx->inv_tmp, &ctx->fri_cols, &ctx->r1cs_arena, &ctx->trace_arena,
                           &ctx->trace_raw, &ctx->fri_misc, &ctx->fri_batch, &ctx->lde_tmp, &ctx->verify_arena,
                           &ctx->verify_lde, &ctx->ext_idx_tmp, &ctx->spot, &ctx->poly, &ctx->prove_batch,
-                          &ctx->verify_batch})
+                          &ctx->verify_batch, &ctx->witness_check})
     total += b->ptr ? b->bytes : 0;
   for (const stark_merkle_tree* t : ctx->trees) total += merkle_device_bytes(t);
   for (const stark_merkle_tree* t : ctx->fri_trees) total += merkle_device_bytes(t);
@@ -442,6 +451,7 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   // stark_prove_r1cs_circuit_batch's forests (its arena is among the buffers above)
   for (const stark_merkle_forest* f : ctx->r1cs_forests) total += forest_device_bytes(f);
   for (const InterpPlan* p : ctx->interp_plans) total += p->bytes;  // the interpolation plans alive on this context
+  for (const LongList* l : ctx->long_lists) total += l->bytes;  // the checked circuits' long-constraint lists
   if (cached_bytes) *cached_bytes = cached;
   if (cache_limit) *cache_limit = ctx->cache_limit;
   if (resident_bytes) *resident_bytes = total;

@@ -171,6 +171,7 @@ constexpr uint32_t kDefaultVerifyLast = 1;
 
 namespace stark {
 struct InterpPlan;
+struct LongList;
 }
 
 struct stark_ctx {
@@ -254,6 +255,12 @@ struct stark_ctx {
   // interp_plan_release takes it out).  stark_ctx_destroy frees what is left and empties those plans, so a handle
   // or a circuit freed after its context finds nothing to free and touches no context memory.
   std::vector<stark::InterpPlan*> interp_plans;
+  // stark_check_r1cs_circuit_batch (r1cs_check.hip): one chunk's working set (raw and Montgomery witness values,
+  // failure bitmaps, counts and records), reused across calls and freed when the prove-batch cap is lowered below
+  // what it holds; and the circuits' long-constraint lists that hold device memory on this context, entered and
+  // emptied like the interpolation plans.
+  stark::DevBuf witness_check;
+  std::vector<stark::LongList*> long_lists;
 };
 
 namespace stark {
@@ -709,6 +716,16 @@ struct PreparedCircuit;
 // out[(k n + i) 32 ..] = column k at g2^positions[i], canonical little-endian.
 stark_status circuit_spot_values(stark_ctx* ctx, const PreparedCircuit& c, const size_t* positions, size_t n,
                                  uint8_t* out, hipStream_t s);
+// The constraints of more than kLongFactor slots of a prepared circuit (r1cs_check.hip: one wave each), built by
+// the circuit's first witness check and freed with the circuit, or with its context if that goes first.
+struct LongList {
+  uint32_t* d = nullptr;
+  uint32_t n = 0;
+  size_t bytes = 0;
+  bool built = false;
+};
+void long_list_release(stark_ctx* ctx, LongList& l);
+void long_lists_release_all(stark_ctx* ctx);
 struct PreparedCircuit {
   DevBuf arena, lde;
   size_t os = 0, n_wires = 0, n_public = 0;
@@ -733,6 +750,7 @@ struct PreparedCircuit {
   // verification that takes it (circuit_public_plan) and freed with the circuit, or with its context if that goes
   // first.  mutable without a lock: a context, and with it its circuits, is driven by one thread at a time.
   mutable InterpPlan pub_plan;
+  mutable LongList long_list;  // (as pub_plan: the first witness check builds it)
   // the circuit's columns with one witness' (circuit_witness: dt holds wit, comp and the public wires)
   TraceView view(const DevTrace& dt) const {
     return {{(const uint64_t*)coef, nullptr, nullptr, nullptr, (const uint64_t*)dt.wit, (const uint64_t*)dt.comp},
@@ -767,6 +785,15 @@ struct WitnessBatchBufs {
 // circuit_witness's device part for a batch: one upload, then decode / fill / running sums with a proof coordinate.
 stark_status circuit_witness_batch(stark_ctx* ctx, const PreparedCircuit& c, const BatchWitness* const* w,
                                    uint32_t batch, const WitnessBatchBufs& bufs, hipStream_t s);
+// circuit_witness's host checks alone (what rejects a witness before anything is enqueued), with the public wires.
+stark_status witness_host_checks(const PreparedCircuit& c, const uint8_t* wtns, size_t wtns_len, BatchWitness* out);
+// The failing constraints of `batch` witnesses past the host checks (r1cs_check.hip), in consecutive chunks under
+// the context's prove-batch limit: witness k's count goes to n_failed[at[k]] and its first min(count, cap) records
+// to failures + at[k] cap.  witness_check_bytes: the device bytes one witness of a chunk takes.
+stark_status check_r1cs_batch(stark_ctx* ctx, const PreparedCircuit& c, const BatchWitness* const* w,
+                              const uint32_t* at, uint32_t batch, uint32_t* n_failed, stark_r1cs_failure* failures,
+                              uint32_t cap);
+size_t witness_check_bytes(const PreparedCircuit& c, uint32_t cap);
 // mk_r1cs_proof for `batch` witnesses of a circuit prepared for world 1 through one launch chain (r1cs.hip
 // prove_r1cs_batch), in consecutive chunks under the context's prove-batch limit.  statuses[b] / out[b]: proof
 // b's status (STARK_OK, or STARK_ERR_CHECK from the constraint kernel's flags) and handle (null unless STARK_OK).
@@ -908,6 +935,7 @@ struct stark_r1cs_circuit {
   stark::PreparedCircuit c;
   ~stark_r1cs_circuit() {
     stark::interp_plan_release(ctx, c.pub_plan);
+    stark::long_list_release(ctx, c.long_list);
     if (c.arena.ptr) hipFree(c.arena.ptr);
     if (c.lde.ptr) hipFree(c.lde.ptr);
   }

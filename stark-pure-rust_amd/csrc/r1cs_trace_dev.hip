@@ -900,8 +900,7 @@ static stark_status circuit_witness(stark_ctx* ctx, const PreparedCircuit& c, co
 }
 
 // circuit_witness's host checks alone (what rejects a witness before anything is enqueued), with the public wires.
-static stark_status witness_host_checks(const PreparedCircuit& c, const uint8_t* wtns, size_t wtns_len,
-                                        BatchWitness* out) {
+stark_status witness_host_checks(const PreparedCircuit& c, const uint8_t* wtns, size_t wtns_len, BatchWitness* out) {
   const FieldHost& F = FieldHost::get();
   WtnsHeader wh;
   STARK_TRY(parse_wtns_header(wtns, wtns_len, &wh));

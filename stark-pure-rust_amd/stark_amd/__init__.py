@@ -163,6 +163,11 @@ _SIGNATURES = {
     "stark_prove_r1cs_circuit": ([_vp, _vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_prove_r1cs_circuit_batch": ([_vp, _vp, ctypes.POINTER(ctypes.c_char_p), _szp, ctypes.c_uint32,
                                         ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+    "stark_check_r1cs_circuit_batch": ([_vp, _vp, ctypes.POINTER(ctypes.c_char_p), _szp, ctypes.c_uint32,
+                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32), _vp,
+                                        ctypes.c_uint32], ctypes.c_int),
+    "stark_check_r1cs_circuit": ([_vp, _vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), _vp,
+                                  ctypes.c_uint32], ctypes.c_int),
     "stark_dprove_circuit_new": ([_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
                                   ctypes.POINTER(_vp)], ctypes.c_int),
     "stark_dprove_begin_circuit": ([_vp, _vp, ctypes.c_char_p, ctypes.c_size_t, _vp, ctypes.POINTER(_vp)],

@@ -282,6 +282,38 @@ def prove_with_witness_host_trace(ctx: Context, r1cs: bytes, wtns: bytes) -> Sta
     return StarkProof(ctx.lib, h)
 
 
+class R1csFailure(ctypes.Structure):
+    """stark_r1cs_failure (include/stark_hip.h): one failing constraint with A.w, B.w and C.w."""
+    _fields_ = [("constraint", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("a", ctypes.c_uint64 * 4),
+                ("b", ctypes.c_uint64 * 4), ("c", ctypes.c_uint64 * 4)]
+
+
+def _limbs_int(v) -> int:
+    return sum(int(x) << (64 * i) for i, x in enumerate(v))
+
+
+class WitnessCheck:
+    """The report of a witness check (R1csCircuit.check): status (0 satisfied, 8 some constraint fails, 3 the
+    witness was refused), n_failed (the exact count) and failures, the first max_failures failing constraints in
+    ascending order as (constraint, a, b, c) with the values A.w, B.w and C.w mod p as Python ints."""
+
+    def __init__(self, status: int, n_failed: int, failures: list):
+        self.status = status
+        self.n_failed = n_failed
+        self.failures = failures
+
+    @property
+    def satisfied(self) -> bool:
+        return self.status == 0
+
+    def __eq__(self, other):
+        return (isinstance(other, WitnessCheck) and
+                (self.status, self.n_failed, self.failures) == (other.status, other.n_failed, other.failures))
+
+    def __repr__(self):
+        return f"WitnessCheck(status={self.status}, n_failed={self.n_failed}, failures={self.failures!r})"
+
+
 class R1csCircuit:
     """A circuit prepared once for many proofs (stark_r1cs_circuit_new): everything of
     prove_with_witness (run.rs:310-452) that depends on the .r1cs alone, including the
@@ -337,6 +369,36 @@ class R1csCircuit:
                     raise x
         return out
 
+    def check_batch(self, wtns_list, max_failures: int = 16) -> list:
+        """A WitnessCheck for every w of wtns_list (stark_check_r1cs_circuit_batch): which constraints each witness
+        fails, without proving anything.  None stands for a missing witness (status 3), as in prove_batch.  An
+        unsatisfied witness does not raise: the report is the result.  Errors of the call as a whole raise
+        StarkError."""
+        ws = [None if w is None else bytes(w) for w in wtns_list]
+        n = len(ws)
+        if n == 0:
+            return []
+        cap = int(max_failures)
+        if cap < 0 or cap > 0xFFFFFFFF:
+            raise StarkError(3, "check_r1cs_circuit_batch", "max_failures out of range")
+        lib = self.ctx.lib
+        ptrs = (ctypes.c_char_p * n)(*ws)
+        lens = (ctypes.c_size_t * n)(*[0 if w is None else len(w) for w in ws])
+        sts = (ctypes.c_int * n)()
+        nf = (ctypes.c_uint32 * n)()
+        recs = (R1csFailure * (n * cap))() if cap else None
+        self.ctx.check(lib.stark_check_r1cs_circuit_batch(self.ctx.h, self.h, ptrs, lens, n, sts, nf, recs, cap),
+                       "check_r1cs_circuit_batch")
+        out = []
+        for b in range(n):
+            fl = [(int(r.constraint), _limbs_int(r.a), _limbs_int(r.b), _limbs_int(r.c))
+                  for r in (recs[b * cap + k] for k in range(min(int(nf[b]), cap)))]
+            out.append(WitnessCheck(int(sts[b]), int(nf[b]), fl))
+        return out
+
+    def check(self, wtns: bytes, max_failures: int = 16) -> WitnessCheck:
+        """check_batch of one witness."""
+        return self.check_batch([wtns], max_failures)[0]
 
     def verify_batch(self, public_wires_list, proofs) -> list:
         """[(status, reasons)] of verify_circuit(public_wires, proof) for every pair, checked on the GPU through
@@ -350,6 +412,11 @@ class R1csCircuit:
                 raise StarkError(3, "verify_batch", "StarkProof handles and proof texts in one list")
             return verify_circuit_batch_proofs(self.ctx, self, public_wires_list, proofs)
         return verify_circuit_batch(self.ctx, self, public_wires_list, proofs)
+
+
+def check_with_witness(ctx: Context, r1cs: bytes, wtns: bytes, max_failures: int = 16) -> WitnessCheck:
+    """Prepares the circuit and checks one witness (R1csCircuit.check)."""
+    return R1csCircuit(ctx, r1cs).check(wtns, max_failures)
 
 
 def prove_with_file_path(ctx: Context, r1cs_file_path: str, witness_file_path: str, proof_json_path: str) -> None:
