@@ -1158,6 +1158,56 @@ extern "C" int stark_test_ntt_plan(stark_ctx* ctx, uint64_t* d_data, uint32_t lo
                          nullptr, plan, policy, used);
 }
 
+// Test hook (not part of the ABI either): stark_test_ntt_plan from a compact source, `batch` columns of
+// 2^(log_n - zero_log) elements (column b at d_src + b 2^(log_n - zero_log), the rest of each column
+// implicitly zero) into d_out (batch columns of 2^log_n).  A zero_log up to the first radix takes that
+// radix's sparse first pass (or its dense one on the compact source, sparse_first), a larger one pad_kernel.
+// Everything is validated before the first launch.
+extern "C" int stark_test_ntt_plan_from(stark_ctx* ctx, const uint64_t* d_src, uint32_t zero_log, uint64_t* d_out,
+                                        uint32_t log_n, uint32_t batch, const uint64_t root[4], int inverse,
+                                        const uint32_t* log_r, uint32_t n_pass, int policy, void* stream,
+                                        uint32_t* used) {
+  using namespace stark;
+  if (!ctx || !d_src || !d_out || (const uint64_t*)d_out == d_src || !root || !log_r || n_pass == 0 || n_pass > 8 ||
+      log_n < 2 || log_n > 28 || zero_log < 1 || zero_log > log_n || batch == 0 || policy < 0 || policy > 3)
+    return STARK_ERR_BAD_ARG;
+  if (((uint64_t)batch << log_n) > ((uint64_t)1 << 34)) return STARK_ERR_BAD_ARG;
+  PassPlan plan;
+  plan.n_pass = (int)n_pass;
+  uint32_t sum = 0;
+  for (uint32_t i = 0; i < n_pass; ++i) {
+    if (log_r[i] < 2 || log_r[i] > kMaxLogR) return STARK_ERR_BAD_ARG;
+    plan.log_r[i] = log_r[i];
+    sum += log_r[i];
+  }
+  if (sum != log_n) return STARK_ERR_BAD_ARG;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const FieldHost& F = FieldHost::get();
+  uint64_t use_root[4];
+  memcpy(use_root, root, 32);
+  if (inverse) F.to_canonical(F.inv(F.from_canonical(root)), use_root);
+  if (used) *used = 0;
+  const Twiddles* tw = nullptr;
+  STARK_TRY(get_twiddles(ctx, use_root, log_n, &tw));
+  return ntt_device_plan(ctx, (const fe*)d_src, zero_log, (fe*)d_out, log_n, batch, *tw, inverse != 0,
+                         pick_stream(ctx, stream), nullptr, plan, policy, used);
+}
+
+// Test hook (not part of the ABI either): ntt_first_pass_tmajor (the cold verifier's first forward pass,
+// T-major) of `batch` compact columns, by the size's own plan; *log_t receives the first radix.
+extern "C" int stark_test_ntt_first_pass_tmajor(stark_ctx* ctx, const uint64_t* d_src, uint32_t zero_log,
+                                                uint64_t* d_out, uint32_t log_n, uint32_t batch,
+                                                const uint64_t root[4], void* stream, uint32_t* log_t) {
+  using namespace stark;
+  if (!ctx || !d_src || !d_out || (const uint64_t*)d_out == d_src || !root || !log_t || log_n < 2 || log_n > 28)
+    return STARK_ERR_BAD_ARG;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  const Twiddles* tw = nullptr;
+  STARK_TRY(get_twiddles(ctx, root, log_n, &tw));
+  return ntt_first_pass_tmajor(ctx, (const fe*)d_src, zero_log, (fe*)d_out, log_n, batch, *tw,
+                               pick_stream(ctx, stream), log_t);
+}
+
 // Test hook (not part of the ABI either): one field primitive of fp_dev.h / fe_mul_asm.inc / fe_db.h or one
 // lazy-range helper of this file per launch, one thread per record, so tests/test_gpu_fe_ops.py places
 // directed operands lane by lane (record i runs in lane i % 64 of wave i / 64).

@@ -1048,6 +1048,29 @@ stark_status stark_verify_r1cs_bytes(stark_ctx* ctx, const uint8_t* r1cs, size_t
   return st;
 }
 
+// Test hook (not part of the ABI of include/stark_hip.h): the cold circuit of stark_verify_r1cs_bytes, built
+// the same way, and circuit_spot_values at the caller's positions (n <= 128, each below the precision): K, F0,
+// F1, F2, IDX, PIDX there, 6 n 32 bytes, column-major as the kernel writes them (sums may exceed p).
+int stark_test_circuit_spot_values(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len, const uint64_t* positions,
+                                   size_t n, uint8_t* out) {
+  if (!ctx || !r1cs || !positions || !out || n == 0 || n > 128) return STARK_ERR_BAD_ARG;  // (128: kSpotMax, r1cs.hip)
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  stark_r1cs_circuit circ;
+  circ.ctx = ctx;
+  std::swap(circ.c.arena, ctx->verify_arena);
+  std::swap(circ.c.lde, ctx->verify_lde);
+  circ.c.with_zb = false;
+  circ.c.spot = true;
+  stark_status st = circuit_build(ctx, r1cs, r1cs_len, circ.c);
+  if (st == STARK_OK) {
+    const std::vector<size_t> pos(positions, positions + n);
+    st = circuit_spot_values(ctx, circ.c, pos.data(), n, out, ctx->stream);
+  }
+  std::swap(circ.c.arena, ctx->verify_arena);
+  std::swap(circ.c.lde, ctx->verify_lde);
+  return st;
+}
+
 stark_status stark_verify_with_witness(stark_ctx* ctx, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* wtns,
                                        size_t wtns_len, const char* proof_json, size_t json_len) {
   if (!ctx || !r1cs || !wtns || !proof_json) return STARK_ERR_BAD_ARG;
