@@ -47,8 +47,9 @@ extern "C" {
  *     stark_ctx_set_verify_batch_transcript.
  * 11: stark_interp_plan_*, stark_lagrange_interp_batch.
  * 12: stark_fri_proof_from_parts, stark_verify_low_degree_batch, stark_ctx_set_verify_batch_last.
- * 13: stark_check_r1cs_circuit(_batch), stark_r1cs_failure. */
-#define STARK_ABI_VERSION 13u
+ * 13: stark_check_r1cs_circuit(_batch), stark_r1cs_failure.
+ * 14: stark_eval_plan_*, stark_eval_poly_multipoint_batch. */
+#define STARK_ABI_VERSION 14u
 /* The ABI version the loaded library implements (no reference counterpart: a linking check). */
 uint32_t stark_abi_version(void);
 /* Paths per SIMD register of the verifier's host Merkle path checks on this CPU (16 AVX-512, 8 AVX2,
@@ -278,6 +279,64 @@ stark_status stark_interp_plan_apply_dev(stark_interp_plan* plan, const uint64_t
  * in the reference): plan, apply, free. */
 stark_status stark_lagrange_interp_batch(stark_ctx* ctx, const uint64_t* xs, const uint64_t* ys, size_t n,
                                          uint32_t batch, uint64_t* out);
+
+/* An evaluation plan: everything of stark_eval_poly_multipoint's tree route that depends on the points and the
+ * degree bound alone -- the subproduct tree's leaf level and transforms and the power-series reciprocal
+ * 1 / rev_N(Z) mod Y^K, K = max_deg_plus_1 padded to a power of two >= 32 -- kept on the device and applied to
+ * `batch` polynomials at once through one chain of launches.  No reference counterpart beyond
+ * calling eval_poly_at (poly_utils.rs:93-102) at every point of xs for each of `batch` polynomials.
+ *   Result.   out[b][i] = sum_k polys[b][k] * xs[i]^k, canonical, bit-identical to stark_eval_poly_at_multi on
+ *             polynomial b (all arithmetic is exact).  A repeated x gives the same value twice; x = 0 gives the
+ *             constant term.
+ *   Degrees.  One plan serves every deg_plus_1 <= max_deg_plus_1 (a shorter polynomial uses a prefix of the
+ *             reciprocal); a longer one is STARK_ERR_BAD_LENGTH.  deg_plus_1 = 0 writes zeros; batch = 0 or
+ *             n = 0 is a no-op.
+ *   Limits.   max_deg_plus_1 = 0 is STARK_ERR_BAD_ARG.  max_deg_plus_1 + N > 2^27, N = n padded to a power of two
+ *             >= 32, is STARK_ERR_BAD_LENGTH (the single call's tree limit), decided before anything is allocated.
+ *             Null pointers where the matching count is non-zero are STARK_ERR_BAD_ARG.
+ *   Memory.   The plan owns 32 B x (n + N + 2 N max(0, log2 N - 5) + 3 K) of device memory, counted in
+ *             stark_ctx_memory's resident_bytes while it lives.  An application takes 32 B x (3 K' + 3 N) of the
+ *             context's scratch per polynomial, K' = deg_plus_1 padded to a power of two >= 32 (and 2 K' once
+ *             where K' < K), and runs in consecutive chunks under stark_ctx_set_prove_batch_limit's cap, at least
+ *             one polynomial each (and at most 65535: any `batch` is served).
+ *   Lifetime. Building takes no host round trip but ends synchronised: the plan returned is complete and usable on
+ *             any stream.  It belongs to its context: stark_ctx_destroy releases the device memory of the plans
+ *             still alive, after which a plan can only be freed (stark_eval_plan_free then frees the handle alone).
+ *   When it pays (profiles/eval_plan_ab.txt; ms per polynomial against single
+ *             stark_eval_poly_multipoint calls): from 16 polynomials at every measured shape (1,024 points against
+ *             1,024 coefficients: 0.025 against 0.070; 8,192 against 2^17: 0.17 against 9.2; 65,536 against 2^20:
+ *             1.35 against 5.8), and from one polynomial at all of them but 1,024 against 1,024, where the single
+ *             call's split Horner takes 0.08 ms and one application 0.34.  Building takes 0.8-4.0 ms once. */
+typedef struct stark_eval_plan stark_eval_plan;
+/* The plan of xs.map(|x| eval_poly_at(., x)) (poly_utils.rs:93-102, called `batch` times in the reference) for
+ * polynomials of up to max_deg_plus_1 coefficients. */
+stark_status stark_eval_plan_new(stark_ctx* ctx, const uint64_t* xs, size_t n, size_t max_deg_plus_1,
+                                 stark_eval_plan** out);
+/* The same for xs[i] = root^exps[i], as stark_interp_plan_new_domain (eval_poly_at, poly_utils.rs:93-102, called
+ * `batch` times in the reference, over r1cs-stark/src/utils.rs:421-436's points): exps[i] < 2^log_order, else
+ * STARK_ERR_BAD_ARG; STARK_ERR_BAD_ROOT for another root.  The points are built on the device. */
+stark_status stark_eval_plan_new_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order,
+                                        const uint64_t* exps, size_t n, size_t max_deg_plus_1, stark_eval_plan** out);
+/* Frees a plan (NULL is a no-op; no reference counterpart: eval_poly_at, poly_utils.rs:93-102, called `batch`
+ * times in the reference, keeps nothing). */
+stark_status stark_eval_plan_free(stark_eval_plan* plan);
+/* eval_poly_at(polys_b, x) for every x of the plan and b < batch (poly_utils.rs:93-102, called `batch` times in
+ * the reference).  Dense: polynomial b's deg_plus_1 coefficients at polys + 4 deg_plus_1 b, low degree first, its
+ * n values at out + 4 n b.  Staged and run a chunk at a time; returns synchronised. */
+stark_status stark_eval_plan_apply(stark_eval_plan* plan, const uint64_t* polys, size_t deg_plus_1, uint32_t batch,
+                                   uint64_t* out);
+/* Device-resident form of the same (eval_poly_at, poly_utils.rs:93-102, called `batch` times in the reference):
+ * polynomial b at d_polys + 4 poly_stride b, its values at d_out + 4 out_stride b; strides in elements,
+ * poly_stride >= deg_plus_1 and out_stride >= n, else STARK_ERR_BAD_ARG.  Buffers are 16-B aligned; input and
+ * output do not overlap; elements between rows are not touched.  Asynchronous on `stream` (NULL = the context
+ * stream), no host synchronisation. */
+stark_status stark_eval_plan_apply_dev(stark_eval_plan* plan, const uint64_t* d_polys, size_t deg_plus_1,
+                                       size_t poly_stride, uint32_t batch, uint64_t* d_out, size_t out_stride,
+                                       void* stream);
+/* `batch` polynomials at one point set (eval_poly_at, poly_utils.rs:93-102, called `batch` times in the
+ * reference): plan with max_deg_plus_1 = deg_plus_1, apply, free, always -- there is no routing threshold inside. */
+stark_status stark_eval_poly_multipoint_batch(stark_ctx* ctx, const uint64_t* polys, size_t deg_plus_1,
+                                              uint32_t batch, const uint64_t* xs, size_t n, uint64_t* out);
 
 /* ---- DFT polynomial products (packages/fri/src/fft.rs) --------------------- */
 /* mul_polys<T>(a, b, root_of_unity) -> Vec<T> (fft.rs:381-395): a (la coefficients) and b (lb) zero-padded

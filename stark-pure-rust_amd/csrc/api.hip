@@ -314,6 +314,7 @@ void stark_ctx_destroy(stark_ctx* ctx) {
   hipDeviceSynchronize();  // (work the caller enqueued on its own streams may still read context buffers)
   ctx->tw.clear();  // (~Twiddles frees the tables)
   interp_plans_release_all(ctx);  // (their handles and circuits may be freed after this: they then hold nothing)
+  eval_plans_release_all(ctx);
   long_lists_release_all(ctx);
   for (stark_merkle_tree*& t : ctx->trees) {
     stark_merkle_free(t);
@@ -451,6 +452,7 @@ stark_status stark_ctx_memory(const stark_ctx* ctx, size_t* cached_bytes, size_t
   // stark_prove_r1cs_circuit_batch's forests (its arena is among the buffers above)
   for (const stark_merkle_forest* f : ctx->r1cs_forests) total += forest_device_bytes(f);
   for (const InterpPlan* p : ctx->interp_plans) total += p->bytes;  // the interpolation plans alive on this context
+  for (const EvalPlan* p : ctx->eval_plans) total += p->bytes;      // the evaluation plans alive on this context
   for (const LongList* l : ctx->long_lists) total += l->bytes;  // the checked circuits' long-constraint lists
   if (cached_bytes) *cached_bytes = cached;
   if (cache_limit) *cache_limit = ctx->cache_limit;

@@ -171,6 +171,7 @@ constexpr uint32_t kDefaultVerifyLast = 1;
 
 namespace stark {
 struct InterpPlan;
+struct EvalPlan;
 struct LongList;
 }
 
@@ -255,6 +256,9 @@ struct stark_ctx {
   // interp_plan_release takes it out).  stark_ctx_destroy frees what is left and empties those plans, so a handle
   // or a circuit freed after its context finds nothing to free and touches no context memory.
   std::vector<stark::InterpPlan*> interp_plans;
+  // The evaluation plans that hold device memory on this context (poly.hip: eval_plan_build / eval_plan_release),
+  // kept and emptied in the same way.
+  std::vector<stark::EvalPlan*> eval_plans;
   // stark_check_r1cs_circuit_batch (r1cs_check.hip): one chunk's working set (raw and Montgomery witness values,
   // failure bitmaps, counts and records), reused across calls and freed when the prove-batch cap is lowered below
   // what it holds; and the circuits' long-constraint lists that hold device memory on this context, entered and
@@ -426,6 +430,38 @@ stark_status poly_tree_eval(stark_ctx* ctx, const PolyTree& t, const fe* d_xs, c
 // Multi-point evaluation on device buffers by the route stark_eval_poly_multipoint documents (takes ctx->poly).
 stark_status eval_multipoint_device(stark_ctx* ctx, const fe* d_poly, size_t deg_plus_1, const fe* d_xs, size_t n,
                                     fe* d_out, hipStream_t s);
+// An evaluation plan: what poly_tree_eval derives from the points and the degree bound alone, in a
+// device buffer of its own: the points (n, canonical), the tree's leaf level z (N), the kept transforms of its
+// `levels` NTT levels (2 N each), alpha = 1 / rev_N(Z_top) mod Y^K as coefficients (K = 2^log_K, the reciprocal's
+// length for max_deg_plus_1 coefficients; a shorter polynomial uses a prefix) and alpha's transform of 2 K points,
+// which an application at that K takes as it is.  Its bytes count in the context's resident bytes.  A plan that holds
+// memory is entered in ctx->eval_plans by its address: it is not copied or moved while built.
+struct EvalPlan {
+  size_t n = 0, N = 0, K = 0, max_deg_plus_1 = 0, bytes = 0;
+  uint32_t log_N = 0, levels = 0, log_K = 0;
+  fe *mem = nullptr, *xs = nullptr, *z = nullptr, *zt = nullptr, *alpha = nullptr, *alpha_t = nullptr;
+};
+// STARK_ERR_BAD_LENGTH where max_deg_plus_1 + N is beyond the tree route's limit (before anything is allocated).
+stark_status eval_plan_check(size_t n, size_t max_deg_plus_1);
+// Builds the plan over the device points d_xs (canonical).  Takes ctx->poly for the tree and the reciprocal; no host
+// round trip but the synchronisation at the end: the plan is complete when it returns.
+stark_status eval_plan_build(stark_ctx* ctx, const fe* d_xs, size_t n, size_t max_deg_plus_1, EvalPlan& plan,
+                             hipStream_t s);
+// Frees the buffer and takes the plan out of ctx->eval_plans; as interp_plan_release for a plan that holds nothing.
+void eval_plan_release(stark_ctx* ctx, EvalPlan& plan);
+// stark_ctx_destroy's part: frees every plan still entered and empties it.
+void eval_plans_release_all(stark_ctx* ctx);
+// Scratch elements of ctx->poly an application takes per polynomial, K' = 2^log_k the reciprocal's length for its
+// deg_plus_1: rev(f) (K'), its product with alpha (2 K'), the vector F (N) and its children's transforms (2 N).
+// A chunk shares 2 K' more (alpha's transform) where K' is below the plan's K.
+inline size_t eval_plan_poly_elems(size_t K1, size_t N) { return 3 * K1 + 3 * N; }
+// Polynomials per chunk of an application (scratch under the prove-batch limit, at least one).
+size_t eval_plan_chunk(const stark_ctx* ctx, const EvalPlan& plan, size_t deg_plus_1, uint32_t batch);
+// Polynomial b's deg_plus_1 coefficients at d_polys + b poly_stride at the plan's points, its n values to
+// d_out + b out_stride (strides in elements): poly_tree_eval's chain for a chunk at a time, the same number of
+// launches as for one polynomial, no host synchronisation.  deg_plus_1 = 0 writes zeros.
+stark_status eval_plan_apply(stark_ctx* ctx, const EvalPlan& plan, const fe* d_polys, size_t deg_plus_1,
+                             size_t poly_stride, uint32_t batch, fe* d_out, size_t out_stride, hipStream_t s);
 // d_xs[i] = root^d_exps[i], canonical (tw = the root's tables).
 stark_status poly_domain_points(stark_ctx* ctx, const Twiddles& tw, const uint64_t* d_exps, size_t n, fe* d_xs,
                                 hipStream_t s);

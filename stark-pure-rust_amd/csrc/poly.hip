@@ -386,6 +386,74 @@ __global__ __launch_bounds__(kPolyThreads) void poly_leaf_eval_kernel(const fe* 
   fe_store(out + g, acc);
 }
 
+// ---- the evaluation plan's kernels: one descent for `batch` polynomials ----
+// Batched arrays are polynomial-major: polynomial b's K' reversed coefficients at b K', its 2 K' product points at
+// 2 b K', its vector F at b N and its children's transforms at 2 b N, so a level's nodes of all polynomials are one
+// contiguous run for the batched transforms.  The plan's alpha^, zt, z and xs are shared by the polynomials.
+// (The compaction is poly_compact_kernel itself over batch N lanes: its child index is then the run's.)
+
+// out[b][i] = f_b[len - 1 - i] for i < len, 0 for len <= i < K' = 2^log_k; f_b at f + b stride (total = batch K').
+__global__ void poly_rev_batch_kernel(const fe* __restrict__ f, uint64_t stride, uint64_t len, uint32_t log_k,
+                                      uint64_t total, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t b = g >> log_k, i = g & (((uint64_t)1 << log_k) - 1);
+  fe_store(out + g, i < len ? fe_load(f + b * stride + (len - 1 - i)) : fe_zero());
+}
+
+// t[b][i] <- t[b][i] at[i] over transforms of m = 2^log_m points (canonical in and out; total = batch m).
+__global__ void poly_shared_mul_kernel(fe* __restrict__ t, const fe* __restrict__ at, uint32_t log_m, uint64_t total,
+                                       fe r2) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const fe a = fe_load(at + (g & (((uint64_t)1 << log_m) - 1)));
+  fe_store(t + g, fe_mul(fe_mul(fe_load(t + g), a), r2));
+}
+
+// poly_root_vec_kernel for every polynomial: out[b][i] = prod_b[i + 1 + d - N], 0 where that index is negative;
+// prod_b has 2^log_p coefficients (total = batch N, N = 2^log_N).
+__global__ void poly_root_vec_batch_kernel(const fe* __restrict__ prod, uint32_t log_p, uint32_t log_N, uint64_t d,
+                                           uint64_t total, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t N = (uint64_t)1 << log_N, b = g >> log_N, i = g & (N - 1);
+  fe_store(out + g, i + 1 + d >= N ? fe_load(prod + (b << log_p) + (i + 1 + d - N)) : fe_zero());
+}
+
+// poly_down_mul_kernel for every polynomial: c counts the children of the whole run (each polynomial has an even
+// number of them, so c / 2 is the run's parent), c & cmask is the child within its polynomial, whose sibling's
+// transform is the plan's.
+__global__ void poly_down_mul_batch_kernel(const fe* __restrict__ ft, const fe* __restrict__ zt, uint32_t log_m,
+                                           uint64_t cmask, uint64_t total, Adj adj, fe r2, fe* __restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const uint64_t mask = ((uint64_t)1 << log_m) - 1, c = g >> log_m, i = g & mask;
+  const fe z = fe_add(fe_load(zt + (((c & cmask) ^ 1) << log_m) + ((0 - i) & mask)), (i & 1) ? adj.odd : adj.even);
+  fe_store(out + g, fe_mul(fe_mul(fe_load(ft + ((c >> 1) << log_m) + i), z), r2));
+}
+
+// poly_leaf_eval_kernel for polynomial blockIdx.y: its vector at fv + b N, its values to out + b out_stride.
+__global__ __launch_bounds__(kPolyThreads) void poly_leaf_eval_batch_kernel(const fe* __restrict__ xs, uint64_t n,
+                                                                            uint64_t N, const fe* __restrict__ z,
+                                                                            const fe* __restrict__ fv, fe r2,
+                                                                            fe* __restrict__ out, uint64_t out_stride) {
+  __shared__ uint32_t zl[8 * kPolyThreads], fl[8 * kPolyThreads];
+  const uint32_t t = threadIdx.x, base = t - (t & (kLeaf - 1));
+  const uint64_t g = (uint64_t)blockIdx.x * kPolyThreads + t, b = blockIdx.y;
+  lds_put(zl, t, g < N ? fe_load(z + g) : fe_zero());
+  lds_put(fl, t, g < N ? fe_mul(fe_load(fv + b * N + g), r2) : fe_zero());  // Montgomery images
+  __syncthreads();
+  if (g >= n) return;
+  const fe x = fe_mul(fe_load(xs + g), r2);
+  fe q = fe_zero(), acc = fe_zero();
+  q.w[0] = 1;
+  for (uint32_t j = kLeaf; j-- > 0;) {
+    if (j + 1 < kLeaf) q = fe_add(lds_get(zl, base + j + 1), fe_mul(q, x));
+    acc = fe_add(acc, fe_mul(q, lds_get(fl, base + j)));
+  }
+  fe_store(out + b * out_stride + g, acc);
+}
+
 // r[i] = a[i] - prod[i] for i < m, 0 for m <= i < fill.
 __global__ void poly_sub_kernel(const fe* __restrict__ a, const fe* __restrict__ prod, uint64_t m, uint64_t fill,
                                 fe* __restrict__ r) {
@@ -825,6 +893,171 @@ stark_status eval_multipoint_device(stark_ctx* ctx, const fe* d_poly, size_t deg
   return buf_release(ctx, ctx->poly, s);
 }
 
+// ---- evaluation plans ----
+
+void eval_plan_release(stark_ctx* ctx, EvalPlan& plan) {
+  if (plan.mem) {  // (then the plan is entered in its context, which is alive: its destruction empties the plans)
+    hipFree(plan.mem);  // (waits for the device: a kernel of any stream may still read it)
+    auto& live = ctx->eval_plans;
+    live.erase(std::remove(live.begin(), live.end(), &plan), live.end());
+  }
+  plan = EvalPlan();
+}
+
+void eval_plans_release_all(stark_ctx* ctx) {
+  for (EvalPlan* p : ctx->eval_plans) {
+    hipFree(p->mem);
+    *p = EvalPlan();
+  }
+  ctx->eval_plans.clear();
+}
+
+stark_status eval_plan_check(size_t n, size_t max_deg_plus_1) {
+  if (n > kMultipointTreeLimit || max_deg_plus_1 > kMultipointTreeLimit) return STARK_ERR_BAD_LENGTH;
+  PolyTree t;
+  poly_tree_plan(n, t);
+  return max_deg_plus_1 + t.N <= kMultipointTreeLimit ? STARK_OK : STARK_ERR_BAD_LENGTH;
+}
+
+// eval_multipoint_device's tree route up to its reciprocal, in ctx->poly, with what an application reads written to
+// the plan's own buffer.  rev_N(Z_top) has constant term 1: the reciprocal needs no inverse from the host.
+stark_status eval_plan_build(stark_ctx* ctx, const fe* d_xs, size_t n, size_t max_deg_plus_1, EvalPlan& plan,
+                             hipStream_t s) {
+  plan = EvalPlan();
+  if (max_deg_plus_1 == 0) return STARK_ERR_BAD_ARG;
+  STARK_TRY(eval_plan_check(n, max_deg_plus_1));
+  plan.max_deg_plus_1 = max_deg_plus_1;
+  if (n == 0) return STARK_OK;
+  const PolyConsts pc = poly_consts();
+  PolyTree t;
+  poly_tree_plan(n, t);
+  const uint32_t log_k = recip_log(max_deg_plus_1);
+  const size_t K = (size_t)1 << log_k, N = t.N, zt_elems = 2 * N * t.levels;
+  fe* own = nullptr;
+  const size_t bytes = (n + N + zt_elems + 3 * K) * sizeof(fe);
+  if (hipMalloc((void**)&own, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return STARK_ERR_OOM;
+  }
+  plan.mem = own;
+  plan.bytes = bytes;
+  ctx->eval_plans.push_back(&plan);
+  plan.n = n;
+  plan.N = N;
+  plan.K = K;
+  plan.log_N = t.log_N;
+  plan.levels = t.levels;
+  plan.log_K = log_k;
+  plan.xs = own;
+  plan.z = plan.xs + n;
+  plan.zt = plan.z + N;
+  plan.alpha = plan.zt + zt_elems;
+  plan.alpha_t = plan.alpha + K;
+  auto build = [&]() -> stark_status {
+    STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+    STARK_TRY(ensure_buf(ctx, ctx->poly, (poly_tree_elems(t) + 5 * K) * sizeof(fe)));
+    fe* mem = (fe*)ctx->poly.ptr;
+    fe* W = mem + poly_tree_elems(t);  // the reciprocal's 4 K, then rev_N(Z_top)
+    STARK_TRY(poly_tree_build(ctx, d_xs, t, mem, s));
+    STARK_HIP(ctx, hipMemcpyAsync(plan.xs, d_xs, n * sizeof(fe), hipMemcpyDeviceToDevice, s));
+    if (zt_elems)
+      STARK_HIP(ctx, hipMemcpyAsync(plan.zt, t.zt, zt_elems * sizeof(fe), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(poly_rev_top_kernel, dim3(grid_for(K)), dim3(256), 0, s, (const fe*)t.z, (uint64_t)N,
+                       t.levels > 0 ? 1 : 0, (uint64_t)K, W + 4 * K);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(poly_recip_device(ctx, W + 4 * K, K, log_k, to_dev(FieldHost::get().one()), plan.alpha, W, s));
+    const Twiddles *fwd, *inv;
+    STARK_TRY(tree_twiddles(ctx, log_k + 1, &fwd, &inv));
+    STARK_TRY(ntt_device_from(ctx, plan.alpha, 1, plan.alpha_t, log_k + 1, 1, *fwd, false, s));
+    // the leaf level (the tree's levels above overwrote theirs; they are taken from their kept transforms)
+    hipLaunchKernelGGL(poly_leaf_kernel<false>, dim3(grid_for(N)), dim3(kPolyThreads), 0, s, d_xs, (const fe*)nullptr,
+                       (const fe*)nullptr, (uint64_t)n, (uint64_t)N, pc.r2, plan.z, (fe*)nullptr);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(buf_release(ctx, ctx->poly, s));
+    // complete on return: the plan is applied on any stream, and d_xs is the caller's staging
+    STARK_HIP(ctx, hipStreamSynchronize(s));
+    return STARK_OK;
+  };
+  const stark_status st = build();
+  if (st != STARK_OK) eval_plan_release(ctx, plan);
+  return st;
+}
+
+// Polynomials per chunk of an application: their scratch (eval_plan_poly_elems) stays under the prove-batch limit,
+// at least one polynomial; a grid's second coordinate, the transforms' 32-bit node count (up to N / 32 per
+// polynomial) and the flat launches' block count (2 K' or 2 N lanes per polynomial) bound a chunk too.
+size_t eval_plan_chunk(const stark_ctx* ctx, const EvalPlan& plan, size_t deg_plus_1, uint32_t batch) {
+  const size_t limit = ctx->prove_batch_limit ? ctx->prove_batch_limit : kDefaultProveBatchLimit;
+  const size_t K1 = (size_t)1 << recip_log(deg_plus_1);
+  const size_t chunk = std::max<size_t>(1, limit / (eval_plan_poly_elems(K1, plan.N) * sizeof(fe)));
+  return std::min<size_t>({chunk, batch, 65535, std::max<size_t>(1, ((size_t)1 << 31) / std::max(plan.N, K1))});
+}
+
+stark_status eval_plan_apply(stark_ctx* ctx, const EvalPlan& plan, const fe* d_polys, size_t deg_plus_1,
+                             size_t poly_stride, uint32_t batch, fe* d_out, size_t out_stride, hipStream_t s) {
+  if (batch == 0 || plan.n == 0) return STARK_OK;
+  if (deg_plus_1 > plan.max_deg_plus_1) return STARK_ERR_BAD_LENGTH;
+  const size_t n = plan.n, N = plan.N;
+  if (deg_plus_1 == 0) {
+    STARK_HIP(ctx, hipMemset2DAsync(d_out, out_stride * sizeof(fe), 0, n * sizeof(fe), batch, s));
+    return STARK_OK;
+  }
+  const PolyConsts pc = poly_consts();
+  const uint32_t log_k = recip_log(deg_plus_1), log_p = log_k + 1;
+  const size_t K1 = (size_t)1 << log_k;
+  const bool prefix = log_k < plan.log_K;  // alpha mod Y^K' is alpha's first K' coefficients: their transform per call
+  const size_t chunk = eval_plan_chunk(ctx, plan, deg_plus_1, batch);
+  STARK_TRY(buf_acquire(ctx, ctx->poly, s));
+  STARK_TRY(ensure_buf(ctx, ctx->poly, (chunk * eval_plan_poly_elems(K1, N) + (prefix ? 2 * K1 : 0)) * sizeof(fe)));
+  fe* R = (fe*)ctx->poly.ptr;   // rev(f_b), K' each
+  fe* T = R + chunk * K1;       // rev(f_b) alpha, 2 K' each
+  fe* fv = T + chunk * 2 * K1;  // F_b, N each
+  fe* G = fv + chunk * N;       // the children's transforms, 2 N each
+  const fe* at = plan.alpha_t;
+  const Twiddles *pf, *pi;
+  STARK_TRY(tree_twiddles(ctx, log_p, &pf, &pi));
+  if (prefix) {
+    fe* At = G + chunk * 2 * N;
+    STARK_TRY(ntt_device_from(ctx, plan.alpha, 1, At, log_p, 1, *pf, false, s));
+    at = At;
+  }
+  for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+    const uint32_t B = (uint32_t)std::min<size_t>(chunk, batch - b0);
+    hipLaunchKernelGGL(poly_rev_batch_kernel, dim3(grid_for((uint64_t)B * K1)), dim3(256), 0, s,
+                       d_polys + (size_t)b0 * poly_stride, (uint64_t)poly_stride, (uint64_t)deg_plus_1, log_k,
+                       (uint64_t)B * K1, R);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(ntt_device_from(ctx, R, 1, T, log_p, B, *pf, false, s));
+    hipLaunchKernelGGL(poly_shared_mul_kernel, dim3(grid_for((uint64_t)B * 2 * K1)), dim3(256), 0, s, T, at, log_p,
+                       (uint64_t)B * 2 * K1, pc.r2);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_TRY(ntt_device(ctx, T, log_p, B, *pi, true, s));
+    hipLaunchKernelGGL(poly_root_vec_batch_kernel, dim3(grid_for((uint64_t)B * N)), dim3(256), 0, s, (const fe*)T, log_p,
+                       plan.log_N, (uint64_t)(deg_plus_1 - 1), (uint64_t)B * N, fv);
+    STARK_HIP(ctx, hipGetLastError());
+    for (uint32_t lv = plan.levels; lv-- > 0;) {
+      const uint32_t log_m = kLeafLog + lv + 1;  // the transforms' size: the parents'
+      const uint32_t parents = (uint32_t)(N >> log_m);
+      const Twiddles *fwd, *inv;
+      STARK_TRY(tree_twiddles(ctx, log_m, &fwd, &inv));
+      STARK_TRY(ntt_device(ctx, fv, log_m, B * parents, *fwd, false, s));
+      hipLaunchKernelGGL(poly_down_mul_batch_kernel, dim3(grid_for((uint64_t)B * 2 * N)), dim3(256), 0, s, (const fe*)fv,
+                         (const fe*)(plan.zt + 2 * N * lv), log_m, (uint64_t)(2 * parents - 1), (uint64_t)B * 2 * N,
+                         level_adj(lv > 0), pc.r2, G);
+      STARK_HIP(ctx, hipGetLastError());
+      STARK_TRY(ntt_device(ctx, G, log_m, B * 2 * parents, *inv, true, s));
+      hipLaunchKernelGGL(poly_compact_kernel, dim3(grid_for((uint64_t)B * N)), dim3(256), 0, s, (const fe*)G, log_m,
+                         (uint64_t)B * N, fv);
+      STARK_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(poly_leaf_eval_batch_kernel, dim3(grid_for(N), B), dim3(kPolyThreads), 0, s, (const fe*)plan.xs,
+                       (uint64_t)n, (uint64_t)N, (const fe*)plan.z, (const fe*)fv, pc.r2,
+                       d_out + (size_t)b0 * out_stride, (uint64_t)out_stride);
+    STARK_HIP(ctx, hipGetLastError());
+  }
+  return buf_release(ctx, ctx->poly, s);
+}
+
 }  // namespace stark
 
 using namespace stark;
@@ -833,6 +1066,12 @@ using namespace stark;
 struct stark_interp_plan {
   stark_ctx* ctx = nullptr;
   stark::InterpPlan p;
+};
+
+// An evaluation plan handle (stark_eval_plan_new): the plan and the context it lives on.
+struct stark_eval_plan {
+  stark_ctx* ctx = nullptr;
+  stark::EvalPlan p;
 };
 
 namespace {
@@ -1066,6 +1305,110 @@ stark_status stark_ctx_set_multipoint_tree_min(stark_ctx* ctx, size_t m) {
   if (!ctx) return STARK_ERR_BAD_ARG;
   ctx->multipoint_tree_min = m;
   return STARK_OK;
+}
+
+stark_status stark_eval_plan_new(stark_ctx* ctx, const uint64_t* xs, size_t n, size_t max_deg_plus_1,
+                                 stark_eval_plan** out) {
+  if (!ctx || !out || (n && !xs) || max_deg_plus_1 == 0) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  STARK_TRY(eval_plan_check(n, max_deg_plus_1));
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<stark_eval_plan> h(new stark_eval_plan);
+  h->ctx = ctx;
+  hipStream_t s = ctx->stream;
+  if (n) {
+    STARK_TRY(ensure_buf(ctx, ctx->io, n * sizeof(fe)));
+    STARK_HIP(ctx, hipMemcpyAsync(ctx->io.ptr, xs, n * sizeof(fe), hipMemcpyHostToDevice, s));
+  }
+  STARK_TRY(eval_plan_build(ctx, (const fe*)ctx->io.ptr, n, max_deg_plus_1, h->p, s));
+  *out = h.release();
+  return STARK_OK;
+}
+
+stark_status stark_eval_plan_new_domain(stark_ctx* ctx, const uint64_t root[4], uint32_t log_order,
+                                        const uint64_t* exps, size_t n, size_t max_deg_plus_1, stark_eval_plan** out) {
+  if (!ctx || !root || !out || (n && !exps) || max_deg_plus_1 == 0) return STARK_ERR_BAD_ARG;
+  *out = nullptr;
+  STARK_TRY(eval_plan_check(n, max_deg_plus_1));
+  if (log_order > 28) return STARK_ERR_BAD_LENGTH;
+  for (size_t i = 0; i < n; ++i)
+    if (exps[i] >> log_order) return STARK_ERR_BAD_ARG;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<stark_eval_plan> h(new stark_eval_plan);
+  h->ctx = ctx;
+  hipStream_t s = ctx->stream;
+  const Twiddles* tw = nullptr;
+  STARK_TRY(get_twiddles(ctx, root, log_order, &tw));
+  fe* d_xs = nullptr;
+  if (n) {  // staging: the points, then their exponents (the build returns synchronised: exps is read by then)
+    STARK_TRY(ensure_buf(ctx, ctx->io, n * (sizeof(fe) + sizeof(uint64_t))));
+    d_xs = (fe*)ctx->io.ptr;
+    uint64_t* d_exps = (uint64_t*)(d_xs + n);
+    STARK_HIP(ctx, hipMemcpyAsync(d_exps, exps, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    STARK_TRY(poly_domain_points(ctx, *tw, d_exps, n, d_xs, s));
+  }
+  STARK_TRY(eval_plan_build(ctx, d_xs, n, max_deg_plus_1, h->p, s));
+  *out = h.release();
+  return STARK_OK;
+}
+
+stark_status stark_eval_plan_free(stark_eval_plan* plan) {
+  if (!plan) return STARK_OK;
+  if (plan->p.mem) (void)hipSetDevice(plan->ctx->device);
+  eval_plan_release(plan->ctx, plan->p);
+  delete plan;
+  return STARK_OK;
+}
+
+stark_status stark_eval_plan_apply_dev(stark_eval_plan* plan, const uint64_t* d_polys, size_t deg_plus_1,
+                                       size_t poly_stride, uint32_t batch, uint64_t* d_out, size_t out_stride,
+                                       void* stream) {
+  if (!plan) return STARK_ERR_BAD_ARG;
+  const size_t n = plan->p.n;
+  if (batch == 0 || n == 0) return STARK_OK;
+  if (!d_out || (deg_plus_1 && !d_polys) || poly_stride < deg_plus_1 || out_stride < n) return STARK_ERR_BAD_ARG;
+  if (deg_plus_1 > plan->p.max_deg_plus_1) return STARK_ERR_BAD_LENGTH;
+  stark_ctx* ctx = plan->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  return eval_plan_apply(ctx, plan->p, (const fe*)d_polys, deg_plus_1, poly_stride, batch, (fe*)d_out, out_stride,
+                         pick_stream(ctx, stream));
+}
+
+stark_status stark_eval_plan_apply(stark_eval_plan* plan, const uint64_t* polys, size_t deg_plus_1, uint32_t batch,
+                                   uint64_t* out) {
+  if (!plan) return STARK_ERR_BAD_ARG;
+  const size_t n = plan->p.n, d = deg_plus_1;
+  if (batch == 0 || n == 0) return STARK_OK;
+  if (!out || (d && !polys)) return STARK_ERR_BAD_ARG;
+  if (d > plan->p.max_deg_plus_1) return STARK_ERR_BAD_LENGTH;
+  stark_ctx* ctx = plan->ctx;
+  STARK_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  // staged a chunk of the application at a time (the coefficients, the values), each chunk behind the last on s
+  const size_t chunk = d ? eval_plan_chunk(ctx, plan->p, d, batch) : std::min<size_t>(batch, 65535);
+  STARK_TRY(ensure_buf(ctx, ctx->io, chunk * (d + n) * sizeof(fe)));
+  fe* d_polys = (fe*)ctx->io.ptr;
+  fe* d_out = d_polys + chunk * d;
+  for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+    const size_t B = std::min<size_t>(chunk, batch - b0);
+    if (d) STARK_HIP(ctx, hipMemcpyAsync(d_polys, polys + 4 * b0 * d, B * d * sizeof(fe), hipMemcpyHostToDevice, s));
+    STARK_TRY(eval_plan_apply(ctx, plan->p, d_polys, d, d, (uint32_t)B, d_out, n, s));
+    STARK_HIP(ctx, hipMemcpyAsync(out + 4 * b0 * n, d_out, B * n * sizeof(fe), hipMemcpyDeviceToHost, s));
+  }
+  STARK_HIP(ctx, hipStreamSynchronize(s));
+  return STARK_OK;
+}
+
+stark_status stark_eval_poly_multipoint_batch(stark_ctx* ctx, const uint64_t* polys, size_t deg_plus_1, uint32_t batch,
+                                              const uint64_t* xs, size_t n, uint64_t* out) {
+  if (!ctx) return STARK_ERR_BAD_ARG;
+  if (n == 0 || batch == 0) return STARK_OK;
+  if (!xs || !out || (deg_plus_1 && !polys)) return STARK_ERR_BAD_ARG;
+  stark_eval_plan* plan = nullptr;
+  STARK_TRY(stark_eval_plan_new(ctx, xs, n, deg_plus_1 ? deg_plus_1 : 1, &plan));
+  const stark_status st = stark_eval_plan_apply(plan, polys, deg_plus_1, batch, out);
+  stark_eval_plan_free(plan);
+  return st;
 }
 
 // div_polys and mod_polys (poly_utils.rs:235-295) in one call.  With b' = b less its trailing zeros (lb'

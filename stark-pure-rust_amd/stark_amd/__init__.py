@@ -80,6 +80,15 @@ _SIGNATURES = {
     "stark_interp_plan_apply": ([_vp, _u64p, ctypes.c_uint32, _u64p], ctypes.c_int),
     "stark_interp_plan_apply_dev": ([_vp, _vp, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
     "stark_lagrange_interp_batch": ([_vp, _u64p, _u64p, ctypes.c_size_t, ctypes.c_uint32, _u64p], ctypes.c_int),
+    "stark_eval_plan_new": ([_vp, _u64p, ctypes.c_size_t, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_eval_plan_new_domain": ([_vp, _u64p, ctypes.c_uint32, _u64p, ctypes.c_size_t, ctypes.c_size_t,
+                                    ctypes.POINTER(_vp)], ctypes.c_int),
+    "stark_eval_plan_free": ([_vp], ctypes.c_int),
+    "stark_eval_plan_apply": ([_vp, _u64p, ctypes.c_size_t, ctypes.c_uint32, _u64p], ctypes.c_int),
+    "stark_eval_plan_apply_dev": ([_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, _vp, ctypes.c_size_t,
+                                   _vp], ctypes.c_int),
+    "stark_eval_poly_multipoint_batch": ([_vp, _u64p, ctypes.c_size_t, ctypes.c_uint32, _u64p, ctypes.c_size_t, _u64p],
+                                         ctypes.c_int),
     "stark_mul_polys": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p],
                         ctypes.c_int),
     "stark_div_polys": ([_vp, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint32, _u64p],
@@ -314,6 +323,14 @@ def _batch_values(ys, n: int) -> np.ndarray:
     """ys as a C-contiguous (batch, n, 4) array (n = 0: one empty vector per entry of ys)."""
     y = np.ascontiguousarray(ys, dtype=np.uint64)
     return y.reshape(-1, n, 4) if n else y.reshape(len(y), 0, 4)
+
+
+def _batch_polys(polys) -> np.ndarray:
+    """polys as a C-contiguous (batch, deg_plus_1, 4) array."""
+    p = np.ascontiguousarray(polys, dtype=np.uint64)
+    if p.ndim != 3 or p.shape[2] != 4:
+        raise ValueError("polys must have shape (batch, deg_plus_1, 4)")
+    return p
 
 
 def _out_array(out, log_n: int) -> np.ndarray:
@@ -597,6 +614,31 @@ class Context:
         finally:
             plan.close()
 
+    def eval_plan(self, xs, max_deg_plus_1: int, root_of_unity=None, log_order_of_root: int = 0) -> "EvalPlan":
+        """What eval_poly_multipoint's tree route derives from the points and the degree bound alone, kept on the
+        device for many polynomials: EvalPlan.apply(polys) evaluates a (batch, deg_plus_1, 4) array at once, for any
+        deg_plus_1 <= max_deg_plus_1.  With root_of_unity, `xs` is a list of exponents, as in lagrange_interp."""
+        h = _vp()
+        if root_of_unity is None:
+            x = _elems(xs)
+            self.check(self.lib.stark_eval_plan_new(self.h, _p64(x), len(x), int(max_deg_plus_1), ctypes.byref(h)),
+                       "eval_plan")
+            return EvalPlan(self, h, len(x), int(max_deg_plus_1))
+        e = np.ascontiguousarray(xs, dtype=np.uint64).reshape(-1)
+        self.check(self.lib.stark_eval_plan_new_domain(self.h, _p64(_limbs(root_of_unity)), log_order_of_root, _p64(e),
+                                                       len(e), int(max_deg_plus_1), ctypes.byref(h)), "eval_plan")
+        return EvalPlan(self, h, len(e), int(max_deg_plus_1))
+
+    def eval_poly_multipoint_batch(self, polys, xs) -> np.ndarray:
+        """[[eval_poly_at(p, x) for x in xs] for p in polys] (poly_utils.rs:93-102) for polys of shape
+        (batch, deg_plus_1, 4): one plan over the points, one application, the same values."""
+        p = _batch_polys(polys)
+        x = _elems(xs)
+        out = np.empty((p.shape[0], len(x), 4), dtype=np.uint64)
+        self.check(self.lib.stark_eval_poly_multipoint_batch(self.h, _p64(p), p.shape[1], p.shape[0], _p64(x), len(x),
+                                                             _p64(out)), "eval_poly_multipoint_batch")
+        return out
+
     def mul_polys(self, a, b, root_of_unity, log_order_of_root: int) -> np.ndarray:
         """fft.rs:381-395: the cyclic product of length 2^log_order_of_root."""
         return self._mul_div(self.lib.stark_mul_polys, "mul_polys", a, b, root_of_unity, log_order_of_root)
@@ -747,6 +789,51 @@ class InterpPlan:
         """The same on device buffers (batch x n elements each), asynchronous on `stream` (0 = the context's)."""
         self.ctx.check(self.ctx.lib.stark_interp_plan_apply_dev(self.h, d_ys, batch, d_out, stream or None),
                        "interp_plan_apply_dev")
+
+
+class EvalPlan:
+    """An evaluation plan over fixed points and a degree bound (Context.eval_plan), held by the library; close()
+    frees it, as does leaving a `with` block.  Closing its context first releases the plan's device memory; close()
+    then frees the handle alone."""
+
+    def __init__(self, ctx, h, n: int, max_deg_plus_1: int):
+        self.ctx = ctx
+        self.h = h
+        self.n = n
+        self.max_deg_plus_1 = max_deg_plus_1
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.stark_eval_plan_free(self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, polys) -> np.ndarray:
+        """polys of shape (batch, deg_plus_1, 4), low degree first -> the values at the plan's points, (batch, n, 4)."""
+        p = _batch_polys(polys)
+        out = np.empty((p.shape[0], self.n, 4), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.stark_eval_plan_apply(self.h, _p64(p), p.shape[1], p.shape[0], _p64(out)),
+                       "eval_plan_apply")
+        return out
+
+    def apply_dev(self, d_polys: int, deg_plus_1: int, poly_stride: int, batch: int, d_out: int, out_stride: int,
+                  stream: int = 0) -> None:
+        """The same on device buffers: polynomial b at d_polys + 32 poly_stride b, its values at d_out +
+        32 out_stride b (strides in elements), asynchronous on `stream` (0 = the context's)."""
+        self.ctx.check(self.ctx.lib.stark_eval_plan_apply_dev(self.h, d_polys, deg_plus_1, poly_stride, batch, d_out,
+                                                              out_stride, stream or None), "eval_plan_apply_dev")
 
 
 class FriProofList:
