@@ -1,6 +1,7 @@
 // C ABI: contexts, buffers, NTT entry points, Blake2s and the index sampler.
 // Each extern "C" function cites the reference item it replaces in
 // include/stark_hip.h.
+#include <atomic>
 #include <new>
 #include <string.h>
 
@@ -18,19 +19,23 @@ stark_status hip_fail(stark_ctx* ctx, hipError_t e, const char* what) {
   return e == hipErrorOutOfMemory ? STARK_ERR_OOM : STARK_ERR_HIP;
 }
 
-// STARK_POISON=1 (diagnostics): every device allocation of the library and every pinned staging buffer
-// is filled with 0xA5 bytes when it is made, so a kernel that reads memory nobody wrote gives a
-// reproducible wrong result instead of one that depends on what the memory held before.
-bool poison_on() {
-  static const bool on = [] {
+// Poison (diagnostics and tests): every device allocation of the library that one upload does not write whole
+// (see stark_test_set_poison below) and every pinned staging buffer is filled with one byte value (0xA5 unless a test sets another) when it is made, so a kernel that reads
+// memory nobody wrote gives a reproducible wrong result instead of one that depends on what the memory held
+// before.  A process-wide flag: STARK_POISON=1 is its initial value, stark_test_set_poison (below) sets it.
+// Bit 8: on; bits 0-7: the byte.
+static std::atomic<int>& poison_state() {
+  static std::atomic<int> state{[] {
     const char* v = getenv("STARK_POISON");
-    return v && v[0] == '1';
-  }();
-  return on;
+    return v && v[0] == '1' ? 0x1A5 : 0;
+  }()};
+  return state;
 }
+bool poison_on() { return (poison_state().load(std::memory_order_relaxed) & 0x100) != 0; }
+int poison_byte() { return poison_state().load(std::memory_order_relaxed) & 0xFF; }
 void poison_dev(void* p, size_t bytes) {
   if (poison_on() && p && bytes) {
-    hipMemset(p, 0xA5, bytes);
+    hipMemset(p, poison_byte(), bytes);
     hipDeviceSynchronize();
   }
 }
@@ -195,7 +200,7 @@ stark_status ctx_pinned(stark_ctx* ctx, int slot, size_t bytes, void** out) {
     const size_t want = bytes < 4096 ? 4096 : bytes;
     // Coherent: kernels read and write this memory directly (zero-copy gathers).
     STARK_HIP(ctx, hipHostMalloc(&ctx->pinned[slot], want, hipHostMallocCoherent));
-    if (poison_on()) memset(ctx->pinned[slot], 0xA5, want);
+    if (poison_on()) memset(ctx->pinned[slot], poison_byte(), want);
     ctx->pinned_bytes[slot] = want;
   }
   *out = ctx->pinned[slot];
@@ -605,6 +610,113 @@ stark_status stark_ctx_synchronize(stark_ctx* ctx) {
   // Every stream the context's buffers were last used on is drained, and no longer referenced.
   for (DevBuf* b : {&ctx->scratch, &ctx->io2, &ctx->fri_misc}) STARK_TRY(buf_drain(ctx, *b));
   return STARK_OK;
+}
+
+// Test hook (not part of the ABI of include/stark_hip.h): the process-wide poison flag (poison_on above).
+// While on, every new pinned buffer of the library and every new device allocation that an upload does not
+// write whole at once is filled with `byte` (the twiddle base tables, the digit-basis tables and the
+// long-constraint lists are one hipMemcpy of their full size behind their hipMalloc: not filled).
+int stark_test_set_poison(int on, int byte) {
+  poison_state().store(on ? 0x100 | (byte & 0xFF) : 0, std::memory_order_relaxed);
+  return STARK_OK;
+}
+
+// Test hook (not part of the ABI either): after a device synchronisation, fills every scratch-class buffer the
+// context holds with `byte`, so that the next call runs on memory that is neither zero nor what its own previous
+// call left (ensure_buf keeps a buffer that is large enough, stale contents included).  report (cap bytes, NUL
+// terminated; STARK_ERR_BAD_LENGTH where it does not fit) receives one line "name bytes class" per buffer:
+// class `scratch` (filled; every call that reads it writes it first) or `kept` (not filled; its contents are an
+// invariant between calls).  ctx null: the names and classes alone.  The kept ones:
+//   tree_counters  the tail kernels' workgroup counters in the last 32 bytes of each tree's node buffer: zeroed
+//                  when the buffer is allocated, left at zero by every launch that uses them (merkle.hip)
+//   tw             the twiddle tables of every (root, log_n) met so far, read by every later transform
+//   ext_idx        the size-only columns shared by every proof of a size (r1cs.hip ext_const_column)
+//   post_tw        the distributed NTT's cached post-twiddles (dist.hip)
+//   interp_plans, eval_plans, long_lists   live tables of handles the caller still holds
+// verify_arena / verify_lde are scratch: stark_verify_r1cs_bytes builds its circuit anew on every call and keeps
+// the two for their allocations only (there is no key to invalidate).  Of a tree or a forest the digest area is
+// filled (trees[], fri_trees, fri_forests, r1cs_forests, verify_forest; their leaves are the callers').  Left
+// out, neither filled nor reported: these trees' `gather` staging (written by every gather before it is copied
+// out) and `own_leaves` (unused by the context's own trees, which hash the callers' device leaves).
+int stark_test_poison_ctx(stark_ctx* ctx, int byte, char* report, size_t cap) {
+  if (cap && !report) return STARK_ERR_BAD_ARG;
+  // ctx null: the report alone (every name and class with 0 bytes), which needs no device.
+  stark_ctx names_only;
+  const bool live = ctx != nullptr;
+  if (!live) ctx = &names_only;
+  if (live) {
+    STARK_HIP(ctx, hipSetDevice(ctx->device));
+    STARK_HIP(ctx, hipDeviceSynchronize());
+  }
+  byte &= 0xFF;
+  std::string rep;
+  const auto line = [&rep](const std::string& name, size_t bytes, const char* cls) {
+    rep += name + " " + std::to_string(bytes) + " " + cls + "\n";
+  };
+  const std::pair<const char*, DevBuf*> bufs[] = {
+      {"scratch", &ctx->scratch},           {"io", &ctx->io},
+      {"io2", &ctx->io2},                   {"fri_cols", &ctx->fri_cols},
+      {"r1cs_arena", &ctx->r1cs_arena},     {"trace_arena", &ctx->trace_arena},
+      {"trace_raw", &ctx->trace_raw},       {"lde_tmp", &ctx->lde_tmp},
+      {"verify_arena", &ctx->verify_arena}, {"verify_lde", &ctx->verify_lde},
+      {"ext_idx_tmp", &ctx->ext_idx_tmp},   {"inv_tmp", &ctx->inv_tmp},
+      {"spot", &ctx->spot},                 {"poly", &ctx->poly},
+      {"fri_misc", &ctx->fri_misc},         {"fri_batch", &ctx->fri_batch},
+      {"prove_batch", &ctx->prove_batch},   {"verify_batch", &ctx->verify_batch},
+      {"witness_check", &ctx->witness_check}};
+  for (const auto& nb : bufs) {
+    const size_t held = nb.second->ptr ? nb.second->bytes : 0;
+    if (held) STARK_HIP(ctx, hipMemset(nb.second->ptr, byte, held));
+    line(nb.first, held, "scratch");
+  }
+  for (int slot = 0; slot < 8; ++slot) {
+    if (ctx->pinned[slot]) memset(ctx->pinned[slot], byte, ctx->pinned_bytes[slot]);
+    line("pinned[" + std::to_string(slot) + "]", ctx->pinned_bytes[slot], "scratch");
+  }
+  size_t counters = 0;
+  for (int slot = 0; slot < 5; ++slot) {
+    const size_t held = merkle_poison_digests(ctx->trees[slot], byte);
+    counters += held ? 32 : 0;
+    line("trees[" + std::to_string(slot) + "]", held > 32 ? held - 32 : 0, "scratch");
+  }
+  size_t held = 0;
+  for (stark_merkle_tree* t : ctx->fri_trees) {
+    const size_t h = merkle_poison_digests(t, byte);
+    counters += h ? 32 : 0;
+    held += h > 32 ? h - 32 : 0;
+  }
+  line("fri_trees", held, "scratch");
+  held = 0;
+  for (stark_merkle_forest* f : ctx->fri_forests) held += forest_poison_digests(f, byte);
+  line("fri_forests", held, "scratch");
+  for (int k = 0; k < 3; ++k)
+    line("r1cs_forests[" + std::to_string(k) + "]", forest_poison_digests(ctx->r1cs_forests[k], byte), "scratch");
+  line("verify_forest", forest_poison_digests(ctx->verify_forest, byte), "scratch");
+  if (live) STARK_HIP(ctx, hipDeviceSynchronize());
+  line("tree_counters", counters, "kept");
+  size_t tw = 0, ext = 0, post = 0, ip = 0, ep = 0, ll = 0;
+  for (const auto& kv : ctx->tw) {
+    tw += kv.second->base_bytes;
+    for (const Twiddles::FullSlot& f : kv.second->full)
+      if (f.ptr) tw += ((size_t)1 << kv.second->log_n) * sizeof(fe);
+  }
+  for (const auto& kv : ctx->ext_idx) ext += kv.second.bytes;
+  for (const auto& kv : ctx->post_tw) post += kv.second.bytes;
+  for (const InterpPlan* p : ctx->interp_plans) ip += p->bytes;
+  for (const EvalPlan* p : ctx->eval_plans) ep += p->bytes;
+  for (const LongList* l : ctx->long_lists) ll += l->bytes;
+  line("tw", tw, "kept");
+  line("ext_idx", ext, "kept");
+  line("post_tw", post, "kept");
+  line("interp_plans", ip, "kept");
+  line("eval_plans", ep, "kept");
+  line("long_lists", ll, "kept");
+  if (cap) {
+    const size_t n = rep.size() < cap ? rep.size() : cap - 1;
+    memcpy(report, rep.data(), n);
+    report[n] = 0;
+  }
+  return rep.size() < cap || !cap ? STARK_OK : STARK_ERR_BAD_LENGTH;
 }
 
 }  // extern "C"

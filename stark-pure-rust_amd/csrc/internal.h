@@ -187,7 +187,8 @@ struct stark_ctx {
   stark::DevBuf trace_arena;  // device trace builder working set (r1cs_trace_dev.hip)
   stark::DevBuf trace_raw;    // the raw constraint section and witness bytes it reads
   stark::DevBuf lde_tmp;      // circuit_lde's step columns and Zb values
-  stark::DevBuf verify_arena, verify_lde;  // the verifier's circuit, kept for the next call
+  // stark_verify_r1cs_bytes' circuit: built anew by every call, kept for the allocations only (scratch contents)
+  stark::DevBuf verify_arena, verify_lde;
   stark::DevBuf ext_idx_tmp;  // an IDX extension too large for the cache cap (this proof only)
   stark::DevBuf inv_tmp;      // the scratch of a second batch inverse sharing a host round trip (r1cs.hip)
   stark::DevBuf spot;         // circuit_spot_values' tables and sums (r1cs.hip)
@@ -282,9 +283,15 @@ stark_status hip_fail(stark_ctx* ctx, hipError_t e, const char* what);
     if (st_ != STARK_OK) return st_; \
   } while (0)
 
-// STARK_POISON=1: fill new device allocations with 0xA5 (api.hip; diagnostics only).
+// Poison: fill new device allocations and pinned buffers with poison_byte() (api.hip; diagnostics and tests:
+// STARK_POISON=1 or stark_test_set_poison).  poison_dev is for an allocation just made, before its first use.
 bool poison_on();
+int poison_byte();
 void poison_dev(void* p, size_t bytes);
+// stark_test_poison_ctx's part for the context's trees and forests (merkle.hip): fills the digest area of the
+// node buffer (a tree's last 32 bytes, its tail kernels' workgroup counter, stay) and returns the bytes held.
+size_t merkle_poison_digests(stark_merkle_tree* t, int byte);
+size_t forest_poison_digests(stark_merkle_forest* f, int byte);
 stark_status ensure_buf(stark_ctx* ctx, DevBuf& b, size_t bytes);
 // Cross-stream use of a context buffer (DevBuf::last): acquire before the first enqueued use on s (s
 // waits for what the previous user's stream has enqueued so far), release after the last one.  A

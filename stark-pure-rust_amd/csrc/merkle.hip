@@ -904,6 +904,19 @@ size_t forest_device_bytes(const stark_merkle_forest* f) {
   return (f->nodes.ptr ? f->nodes.bytes : 0) + (f->own_leaves.ptr ? f->own_leaves.bytes : 0);
 }
 
+// (the caller has synchronised the device)
+size_t merkle_poison_digests(stark_merkle_tree* t, int byte) {
+  if (!t || !t->nodes.ptr) return 0;
+  if (t->nodes.bytes > 32) hipMemset(t->nodes.ptr, byte, t->nodes.bytes - 32);  // (tail_counter stays)
+  return t->nodes.bytes;
+}
+
+size_t forest_poison_digests(stark_merkle_forest* f, int byte) {
+  if (!f || !f->nodes.ptr) return 0;
+  if (f->nodes.bytes) hipMemset(f->nodes.ptr, byte, f->nodes.bytes);  // (digests only: a forest has no counter)
+  return f->nodes.bytes;
+}
+
 }  // namespace stark
 
 using namespace stark;

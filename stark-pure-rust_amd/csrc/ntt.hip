@@ -1072,6 +1072,7 @@ static stark_status full_table(stark_ctx* ctx, const Twiddles& tw_c, uint32_t ki
       *out = nullptr;     // no room
       return STARK_OK;
     }
+    poison_dev(p, n * sizeof(fe));
     if (kind == Twiddles::kFullFused)
       hipLaunchKernelGGL(fused_tw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tw.d_lo, tw.d_hi,
                          tw.kb, tw.log_n, to_dev(tw.inv_n), scaled ? 1 : 0, (fe*)p);

@@ -638,6 +638,7 @@ stark_status interp_plan_build(stark_ctx* ctx, const fe* d_xs, size_t n, const D
     (void)hipGetLastError();
     return STARK_ERR_OOM;
   }
+  poison_dev(own, bytes);
   plan.mem = own;
   plan.bytes = bytes;
   ctx->interp_plans.push_back(&plan);
@@ -939,6 +940,7 @@ stark_status eval_plan_build(stark_ctx* ctx, const fe* d_xs, size_t n, size_t ma
     (void)hipGetLastError();
     return STARK_ERR_OOM;
   }
+  poison_dev(own, bytes);
   plan.mem = own;
   plan.bytes = bytes;
   ctx->eval_plans.push_back(&plan);

@@ -1103,6 +1103,7 @@ static stark_status ext_const_column(stark_ctx* ctx, uint32_t kind, uint64_t os,
       }
       return STARK_ERR_OOM;
     }
+    poison_dev(col, P * sizeof(fe));
     ctx->ext_idx[key] = CacheBuf{col, P * sizeof(fe), ++ctx->cache_clock};  // counted while it is built
   } else if (kind != kExtIdx) {
     *out = nullptr;
@@ -1124,6 +1125,7 @@ static stark_status ext_const_column(stark_ctx* ctx, uint32_t kind, uint64_t os,
     drop();
     return STARK_ERR_OOM;
   }
+  poison_dev(coef, tmp_n * sizeof(fe));
   stark_status st = STARK_OK;
   if (inv) {  // r1cs_zb_kernel with no public points: Zb2 = 1 (unused), x - c in the second half
     const FieldHost& F = FieldHost::get();

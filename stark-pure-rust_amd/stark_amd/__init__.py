@@ -252,6 +252,13 @@ _SIGNATURES = {
                                    ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
 }
 
+# Test hooks the library exports beside its ABI (not declared in include/stark_hip.h): the poison flag and the
+# fill of a context's scratch (csrc/api.hip).
+_TEST_HOOKS = {
+    "stark_test_set_poison": ([ctypes.c_int, ctypes.c_int], ctypes.c_int),
+    "stark_test_poison_ctx": ([_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
+}
+
 _lib = None
 
 
@@ -264,7 +271,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         raise RuntimeError(f"libstark_hip.so not built at {path}: run `make -C stark-pure-rust_amd` "
                            "or __graft_entry__.build()")
     lib = ctypes.CDLL(path)
-    for name, (args, res) in _SIGNATURES.items():
+    for name, (args, res) in list(_SIGNATURES.items()) + list(_TEST_HOOKS.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
@@ -281,6 +288,24 @@ def header_abi_version(path: str = HEADER_PATH) -> int:
     import re
     m = re.search(r"#define\s+STARK_ABI_VERSION\s+(\d+)u?", open(path).read())
     return int(m.group(1))
+
+
+def set_poison(on: bool, byte: int = 0xA5) -> None:
+    """Test hook: while on, every new device allocation and pinned buffer of the library is filled with `byte`
+    (process-wide; STARK_POISON=1 is the flag's initial value)."""
+    load_library().stark_test_set_poison(1 if on else 0, int(byte))
+
+
+def poison_ctx(ctx, byte: int) -> list:
+    """Test hook: synchronises the device, fills every scratch-class buffer of `ctx` with `byte` and returns the
+    report as (name, bytes held, class) per context buffer; class "scratch" (filled) or "kept" (not filled).
+    ctx None: the names and classes alone (no device needed)."""
+    lib = load_library()
+    buf = ctypes.create_string_buffer(8192)
+    rc = lib.stark_test_poison_ctx(ctx.h if ctx is not None else None, int(byte), buf, len(buf))
+    if rc != 0:
+        raise StarkError(rc, "stark_test_poison_ctx")
+    return [(n, int(b), c) for n, b, c in (ln.split() for ln in buf.value.decode().splitlines())]
 
 
 HIP_STREAM_LEGACY = 1  # hipStreamLegacy (hip_runtime_api.h): the legacy default stream as a handle
